@@ -19,14 +19,21 @@ in HBM -> Arrow values buffer in HBM).  value = decoded bytes of all ranks /
 max-over-ranks wall time of the timed steps.  Weak scaling: each rank owns a
 100M-row shard (its own page queue, no collectives on the data path).
 
-Also reported: the all-Bitpacking b=12 variant (the north star's >=60 %
-roofline target), the harder C2 mix, configs 3-5 (Float64 + Utf8 under LZ4;
-List<Int32>; the 64-column mixed table, encoded on the GPU and checked byte
-for byte against the host writer), device encode rates, and per config the
-CPU restatement of the reference's src/read decoder (oracle/, the
-reference's algorithms with system liblz4 / libzstd) timed on 1 host thread
-(the reference's shape) and on all the box's cores (pages sharded over
-threads), with the CPU model.
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) builds that column,
+warms up, times the N steps and prints the result line: nothing else.
+--dump-outputs DIR then writes what the last timed step decoded
+(DIR/values.npy, see dump_outputs); the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
+
+With --full also reported: the all-Bitpacking b=12 variant (the north
+star's >=60 % roofline target), the harder C2 mix, configs 3-5 (Float64 +
+Utf8 under LZ4; List<Int32>; the 64-column mixed table, encoded on the GPU
+and checked byte for byte against the host writer), device encode rates, the
+file -> HBM -> Arrow pipeline, and per config the CPU restatement of the
+reference's src/read decoder (oracle/, the reference's algorithms with
+system liblz4 / libzstd) timed on 1 host thread (the reference's shape) and
+on all the box's cores (pages sharded over threads), with the CPU model.
+The --no-* options drop single legs of a --full run.
 """
 from __future__ import annotations
 
@@ -242,6 +249,33 @@ def timed(torch, dist, wl: Workload, steps: int, warmup: int):
         d.check()
     kern_ms = [e0.elapsed_time(e1) / steps]
     return t1 - t0, kern_ms, ok
+
+
+DUMP_ROWS = 4 * 1024 * 1024  # rows per dumped array: 32 MiB of float64
+DUMP_SEED = 20240607
+
+
+def dump_outputs(torch, wl: Workload, steps: int, out_dir: str, world: int, rank: int) -> dict:
+    """Writes what the last timed step decoded -- the values buffer a caller
+    of decode_async receives (the column is non-nullable: there is no
+    validity buffer) -- as out_dir/values.npy (values_rank<r>.npy for the
+    ranks of an N > 1 run), float64 (exact for Int32).  A column of more than
+    DUMP_ROWS rows is sampled: the rows are cut into DUMP_ROWS equal strata
+    and one row drawn from each with a fixed seed, the same rows on every
+    run with the same arguments (about 340 of every 8192-row page at the
+    default size)."""
+    vals = wl.outs[(steps - 1) & 1][0][: wl.rows]
+    sampled = wl.rows > DUMP_ROWS
+    if sampled:
+        edges = np.arange(DUMP_ROWS + 1, dtype=np.int64) * wl.rows // DUMP_ROWS
+        pick = np.random.default_rng(DUMP_SEED).random(DUMP_ROWS)
+        idx = edges[:-1] + (pick * (edges[1:] - edges[:-1])).astype(np.int64)
+        vals = vals[torch.from_numpy(idx).to(vals.device)]
+    arr = vals.cpu().numpy().astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    name = "values.npy" if world == 1 else f"values_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), arr)
+    return {"file": name, "rows": int(arr.size), "of_rows": wl.rows, "sampled": sampled, "dtype": "float64"}
 
 
 def encode_gpu(torch, pa, rows: int, device: int, threads: int, steps: int) -> dict:
@@ -1132,6 +1166,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rows", type=int, default=100_000_000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one decoded to DIR/values.npy "
+                         "(float64; a fixed seeded sample of a large column)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: file pipeline, harder C2 mix, b=12, configs 3-5, "
+                         "device encode, CPU baselines (each can be dropped with its --no-* option)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-b12", action="store_true", help="skip the all-bitpack b=12 variant")
     ap.add_argument("--no-hard", action="store_true", help="skip the harder C2 mix (b 12..24, RLE runs of 2-3)")
@@ -1145,6 +1185,11 @@ def main():
     ap.add_argument("--c5-rows", type=int, default=8_388_608)
     ap.add_argument("--no-file", action="store_true", help="skip the file -> HBM -> Arrow pipeline measurement")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run is the headline alone
+        args.no_cpu = args.no_file = args.no_hard = args.no_b12 = args.no_c3 = args.no_c4 = args.no_c5 = True
+        args.no_encode = True
 
     import torch
 
@@ -1189,6 +1234,7 @@ def main():
     achieved = (wl.in_bytes + wl.out_bytes) / (kavg / 1e3) / 1e9
     total_out = reduce(float(wl.out_bytes), SUM)
     value = total_out * args.steps / wall_max / 1e9
+    dumped = dump_outputs(torch, wl, args.steps, args.dump_outputs, world, rank) if args.dump_outputs else None
 
     extra = {}
     if not args.no_file and world == 1:
@@ -1350,6 +1396,8 @@ def main():
             },
         }
         line.update(extra)
+        if dumped:
+            line["dumped_outputs"] = dumped
         if do_cpu:
             line["cpu_baseline"] = cpu_baseline(wl)
         print(json.dumps(line), flush=True)

@@ -1,7 +1,8 @@
 #!/bin/bash
 # One GPU round trip: the -m gpu suite, then the Patas column bench (and its
-# phase variant when built), then a C5-only bench line.  Each step under its
-# own time limit; the first failure ends the script.
+# phase variant when built), then a bench line when BENCH_ARGS is set (give
+# --full with the --no-* options for a single leg, such as C5 alone).  Each
+# step under its own time limit; the first failure ends the script.
 set -o pipefail
 mkdir -p gpurun_out
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > gpurun_out/gpu_tests.log 2>&1 || { tail -30 gpurun_out/gpu_tests.log; exit 1; }
