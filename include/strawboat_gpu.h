@@ -393,8 +393,10 @@ uint64_t sb_zstd_compress_host(const uint8_t* src, uint64_t n, uint8_t* dst);
  * sb_encode_column with the same options: the adaptive cascade
  * (compress_integer / compress_double / compress_boolean with the seeded
  * trial-window sampler, forced codecs, Dict / Freq cascades, Patas) and the
- * Basic codecs None / LZ4 / Snappy run on the GPU; a Zstd default codec that a
- * page needs reports SB_E_NYI (libzstd's compressor is not restated).
+ * Basic codecs None / LZ4 / Snappy run on the GPU; a Zstd default codec writes
+ * the device's own frames (pa_amd/csrc/sb_zstdc.h: any Zstd decoder returns the
+ * page's bytes, libzstd's are not reproduced; pages, codec choices and
+ * num_values equal the host writer's).
  * Options with ratio None + default None (+ forced Bitpacking) take a
  * dedicated sizing/assembly fast path.  d_values (Boolean: the column's LSB
  * bitmap) / d_validity (column LSB bitmap) / d_out are device memory; d_out
@@ -412,9 +414,10 @@ sb_status sb_encode_column_device(sb_ctx* ctx, int32_t physical_type, const void
  * sb_encode_binary_column); d_validity the column's LSB bitmap.  The writer's
  * full option set runs on the device (compress_binary, binary/mod.rs:26-93:
  * OneValue / Freq / Dict by ratio or forced, the Dict index stream through the
- * integer cascade, Basic None / LZ4 / Snappy) except a Zstd default codec
- * (SB_E_NYI); byte-identical to sb_encode_binary_column.  d_out holds at
- * least sb_encode_binary_device_bound() bytes.  Synchronizes the stream. */
+ * integer cascade, Basic None / LZ4 / Snappy); byte-identical to
+ * sb_encode_binary_column, but for the frames of a Zstd default codec (the
+ * device's own, as sb_encode_column_device).  d_out holds at least
+ * sb_encode_binary_device_bound() bytes.  Synchronizes the stream. */
 uint64_t sb_encode_binary_device_bound(int32_t physical_type, uint64_t n_rows, uint64_t values_len, int32_t nullable,
                                        uint64_t max_page_rows);
 sb_status sb_encode_binary_column_device(sb_ctx* ctx, int32_t physical_type, const uint8_t* d_values,
@@ -443,6 +446,40 @@ sb_status sb_encode_list_column_device(sb_ctx* ctx, int32_t physical_type, const
                                        const sb_write_options* opts, uint64_t max_page_rows, uint8_t* d_out,
                                        uint64_t out_capacity, uint64_t* out_len, sb_page_meta* h_metas,
                                        uint64_t metas_cap, uint64_t* n_pages);
+/* One nest of a leaf path in device memory: as sb_nest_in. */
+typedef struct {
+  const int64_t* d_offsets;
+  const uint8_t* d_validity;
+} sb_nest_dev;
+/* encode_chunk for one leaf column of ANY nested field on the device:
+ * sb_encode_nested_column with every buffer in HBM and the chunk written to
+ * d_out.  desc: depth 1..SB_MAX_NEST (else SB_E_NYI), struct_mask, per-nest
+ * nullable and item_nullable; a nullable nest or leaf must bring its bitmap.
+ * The leaf: fixed width, Boolean (d_values = the LSB bitmap of its slots) or
+ * Binary / Utf8 / Large* (d_leaf_offsets = slots + 1 absolute int64 positions
+ * into d_values; values_len = the whole buffer, which the Extend header and
+ * the statistics use).  Pages of max_page_rows (<= 16384, else SB_E_NYI)
+ * top-level rows; the Dremel levels of each page come from per-nest level
+ * prefixes in context scratch (k_nest_levels), the page's leaf slice goes
+ * through sb_encode_column_device's / sb_encode_binary_column_device's page
+ * kernels behind its level header.  Byte-identical to sb_encode_nested_column
+ * under default None / LZ4 / Snappy and every ratio / forced-codec option; a
+ * Zstd default codec writes the device's own frames.  PageMeta.num_values =
+ * the page's level count; page p samples with sb_page_seed(opts->seed, p).
+ * SB_E_ARG: NULL ctx / opts / output pointers, a missing bitmap, offsets that
+ * decrease (or are negative) at any nest or at the leaf, a d_out or metas_cap
+ * too small.  d_out holds at least sb_encode_nested_device_bound(..) bytes:
+ * n_level_bound = the entries of every nest + the leaf slots (no page holds
+ * more levels), n_leaf = the leaf slots; host only.  Synchronizes the
+ * context's stream. */
+uint64_t sb_encode_nested_device_bound(const sb_nested_desc* desc, uint64_t n_rows, uint64_t n_level_bound,
+                                       uint64_t n_leaf, uint64_t values_len, uint64_t max_page_rows);
+sb_status sb_encode_nested_column_device(sb_ctx* ctx, const sb_nested_desc* desc, const sb_nest_dev* d_nests,
+                                         const void* d_values, const int64_t* d_leaf_offsets, uint64_t values_len,
+                                         const uint8_t* d_leaf_validity, uint64_t n_rows,
+                                         const sb_write_options* opts, uint64_t max_page_rows, uint8_t* d_out,
+                                         uint64_t out_capacity, uint64_t* out_len, sb_page_meta* h_metas,
+                                         uint64_t metas_cap, uint64_t* n_pages);
 /* NativeWriter::finish (write/writer.rs:128-167) footer bytes. */
 sb_status sb_write_footer(const uint8_t* h_schema, uint64_t schema_len, const uint64_t* h_col_offsets,
                           const uint64_t* h_col_npages, uint64_t n_cols, const sb_page_meta* h_pages,

@@ -22,7 +22,8 @@ from .binary import (  # noqa: F401,E402
     encode_binary_column_device,
 )
 from .nested import (DeviceArray, Field, FieldDecoder, HostArray, ListColumnDecoder, NestedColumnDecoder,  # noqa: F401,E402
-                     batch_read_field, batch_read_list, encode_field, encode_list_column, encode_list_column_device)
+                     batch_read_field, batch_read_list, device_array, encode_field, encode_field_device,
+                     encode_list_column, encode_list_column_device)
 from .file import Leaf, StrawboatFile, parse_schema  # noqa: F401,E402
 from .table import ColumnGroupDecoder  # noqa: F401,E402
 from .stream import PageArray, decode_columns, iter_page_arrays, to_host  # noqa: F401,E402

@@ -33,6 +33,7 @@ EXPORTED = [
     "sb_file_last_error", "sb_file_num_columns", "sb_file_column", "sb_file_schema", "sb_file_upload",
     "sb_decode_page_validity", "sb_decode_page_levels", "sb_plan_column_at",
     "sb_encode_list_device_bound", "sb_encode_list_column_device", "sb_encode_nested_column",
+    "sb_encode_nested_device_bound", "sb_encode_nested_column_device",
 ]
 
 MAX_NEST = 4

@@ -26,10 +26,17 @@
 //     Snappy (one lane) / Zstd (sb_zstdc.h: frames transcoded from the LZ4
 //     parse; libzstd level 3's bytes are not reproduced, any Zstd decoder
 //     returns the page's bytes).
+// Binary / Utf8 and Boolean pages have their own page kernels (k_enc_binary,
+// k_enc_bool); nested leaves run the same kernels over each page's leaf
+// slice behind its level header (k_enc_list_levels for List<primitive>,
+// k_nest_levels for any Struct / Map / List chain).
 // Pages are written into per-page slots of a batch, then compacted.
 // Integer work; bound by the per-page hash/scan work, not by MFMA.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
+
+#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <vector>
@@ -1128,6 +1135,7 @@ struct AdArgs {
   const uint8_t* heads = nullptr;
   uint64_t head_slot = 0;
   const uint32_t* head_len = nullptr;
+  const uint64_t* head_at = nullptr;  // nested pages: page p's header at heads + head_at[p] (variable slots)
 };
 
 // Page p's rows: [p * P, min((p + 1) * P, n_rows)), or a List page's child values
@@ -1144,8 +1152,9 @@ __device__ __forceinline__ void page_rows(const AdArgs& A, uint32_t p, uint64_t*
 // A List page's level header, copied to the page's start by the threads of
 // `nt`; returns its length
 __device__ __forceinline__ uint32_t put_head(const AdArgs& A, uint32_t p, uint8_t* out, uint32_t nt) {
-  const uint32_t hl = (uint32_t)min<uint64_t>(A.head_len[p], A.head_slot);  // never past the header's slot
-  const uint8_t* h = A.heads + (uint64_t)p * A.head_slot;
+  const uint64_t hcap = A.head_at ? A.head_at[p + 1] - A.head_at[p] : A.head_slot;
+  const uint32_t hl = (uint32_t)min<uint64_t>(A.head_len[p], hcap);  // never past the header's slot
+  const uint8_t* h = A.heads + (A.head_at ? A.head_at[p] : (uint64_t)p * A.head_slot);
   for (uint32_t j = threadIdx.x; j < hl; j += nt) out[j] = h[j];
   return hl;
 }
@@ -1240,8 +1249,9 @@ __global__ __launch_bounds__(NT) void k_enc_bool(AdArgs A) {
   __shared__ Sh sh;
   const uint32_t tid = threadIdx.x;
   const uint32_t p = A.page0 + blockIdx.x;
-  const uint64_t r0 = (uint64_t)p * A.P;
-  const uint32_t n = (uint32_t)min<uint64_t>(A.P, A.n_rows - r0);
+  uint64_t r0;  // (a nested page: its leaf slice, whose first bit need not start a byte)
+  uint32_t n;
+  page_rows(A, p, &r0, &n);
   Ctx c;
   ctx_init(c, sh, A, p);
   uint8_t* vals;
@@ -1267,7 +1277,7 @@ __global__ __launch_bounds__(NT) void k_enc_bool(AdArgs A) {
       rebuilt[j] = (uint8_t)v;
     }
   const bool has_vb = A.nullable && A.validity;
-  uint32_t pos = write_prefix(c, A, r0, n);
+  uint32_t pos = A.heads ? put_head(A, p, c.out, NT) : write_prefix(c, A, r0, n);
   const Av a{vals, has_vb ? A.validity : nullptr, r0, n};
   uint32_t t = 0, f = 0;
   for (uint32_t i = tid; i < n; i += NT)
@@ -1530,8 +1540,9 @@ __global__ __launch_bounds__(NT) void k_enc_binary(AdArgs A) {
   __shared__ Sh sh;
   const uint32_t tid = threadIdx.x;
   const uint32_t p = A.page0 + blockIdx.x;
-  const uint64_t r0 = (uint64_t)p * A.P;
-  const uint32_t n = (uint32_t)min<uint64_t>(A.P, A.n_rows - r0);
+  uint64_t r0;
+  uint32_t n;
+  page_rows(A, p, &r0, &n);
   Ctx c;
   ctx_init(c, sh, A, p);
   set_work(c, A, lds);
@@ -1544,7 +1555,7 @@ __global__ __launch_bounds__(NT) void k_enc_binary(AdArgs A) {
   auto sptr = [&](uint32_t r) { return A.values + A.offsets[r0 + r]; };
   const bool has_vb = A.nullable && A.validity;
   const Av va{nullptr, has_vb ? A.validity : nullptr, r0, n};
-  uint32_t pos = write_prefix(c, A, r0, n);
+  uint32_t pos = A.heads ? put_head(A, p, c.out, NT) : write_prefix(c, A, r0, n);
   auto same = [&](uint32_t a, uint32_t b) {
     if (hsh[a] != hsh[b]) return false;
     const uint32_t l = slen(a);
@@ -1948,6 +1959,179 @@ __global__ __launch_bounds__(NT) void k_enc_list_levels(ListLv a) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// Any nest chain over a leaf (write_nested, serialize.rs:135-198; the host
+// writer's LevelWalk, sb_encode.cpp): the Dremel levels of one leaf path,
+// data-parallel.  cnt_d[i] = the levels slot i of nest d emits (a null slot
+// or an empty list 1, a struct slot its child slot's, a list slot the sum of
+// its children's); C_d = the column-wide exclusive prefix of cnt_d, count_d +
+// 1 entries (k_nest_counts + a device scan per nest, bottom-up; the leaf's
+// prefix is the identity and is not stored, nor is that of a chain that
+// emits one level per slot).  Level k of the column is then found by
+// descending the nests with a binary search in C_{d + 1} over each list
+// slot's children: def accumulates to where the walk stops, rep is the
+// cumulative repetition level under the deepest list nest at which the
+// chosen child is not its list's first.  Page p's levels are [C_0[r0],
+// C_0[r0 + m)): their count is not bounded by the rows, so nothing of a page
+// is staged in LDS; one workgroup per page packs 32-level chunks per thread.
+// ---------------------------------------------------------------------------
+struct NestLv {
+  int depth;
+  uint32_t struct_mask, null_mask;  // bit d: nest d is a Struct / is nullable
+  int leaf_nullable;
+  const int64_t* offs[4];   // list nests: count_d + 1 absolute positions
+  const uint8_t* valid[4];  // nullable nests: bitmap over the nest's slots
+  const uint64_t* C[5];     // C_d (count_d + 1 entries), nullptr = the identity
+  const uint8_t* leaf_valid;
+  uint64_t n_rows;
+  uint32_t step;
+  uint32_t bw_rep, bw_def;  // 0 = no stream (a max level of 0)
+  const uint64_t* lv_at;    // [np + 1]: C_0 at the page boundaries
+  const uint64_t* head_at;  // [np + 1]: page p's header slot in heads
+  uint8_t* heads;
+  uint32_t* head_len;
+};
+
+__device__ __forceinline__ uint64_t pre_at(const uint64_t* C, uint64_t i) { return C ? C[i] : i; }
+
+// offsets [0, count]: non-negative and non-decreasing, else *bad; res[1] = o[count]
+__global__ void k_nest_check(const int64_t* o, uint64_t count, uint64_t* res) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count && (o[i] < 0 || o[i + 1] < o[i])) res[0] = 1;
+  if (i == count) res[1] = (uint64_t)o[count];
+}
+
+// cnt_d over nest d's slots into out[0, count) (out[count] = 0: the scan's total lands there)
+__global__ void k_nest_counts(const int64_t* o, const uint8_t* valid, const uint64_t* Cc, uint64_t count,
+                              uint64_t* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > count) return;
+  uint64_t c = 0;
+  if (i < count) {
+    if (valid && !bit_at(valid, i)) {
+      c = 1;
+    } else if (!o) {  // a struct slot: its child slot's levels
+      c = pre_at(Cc, i + 1) - pre_at(Cc, i);
+    } else {
+      const uint64_t b = (uint64_t)o[i], e = (uint64_t)o[i + 1];
+      c = b == e ? 1 : pre_at(Cc, e) - pre_at(Cc, b);
+    }
+  }
+  out[i] = c;
+}
+
+// page boundaries: the level prefix and the leaf slot each one reaches
+__global__ void k_nest_bounds(NestLv a, uint64_t np, uint64_t* lv_at, uint64_t* rows_at) {
+  const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p > np) return;
+  uint64_t j = min(p * (uint64_t)a.step, a.n_rows);
+  lv_at[p] = pre_at(a.C[0], j);
+  for (int d = 0; d < a.depth; d++)
+    if (!((a.struct_mask >> d) & 1)) j = (uint64_t)a.offs[d][j];
+  rows_at[p] = j;
+}
+
+// level k of the column: rep | def << 8
+__device__ uint32_t nest_level(const NestLv& a, uint64_t r0, uint32_t m, uint64_t k) {
+  // the last row of the page with C_0[row] <= k
+  uint64_t idx;
+  if (a.C[0]) {
+    uint64_t lo = r0, hi = r0 + m;
+    while (hi - lo > 1) {
+      const uint64_t mid = (lo + hi) >> 1;
+      if (a.C[0][mid] <= k) lo = mid;
+      else hi = mid;
+    }
+    idx = lo;
+  } else {
+    idx = k;
+  }
+  uint64_t rem = k - pre_at(a.C[0], idx);  // the level sought among those of slot idx
+  uint32_t rep = 0, def = 0, lists = 0;
+  for (int d = 0; d < a.depth; d++) {
+    const bool nullable = (a.null_mask >> d) & 1;
+    if (nullable && !bit_at(a.valid[d], idx)) return rep | (def << 8);
+    def += nullable;
+    if ((a.struct_mask >> d) & 1) continue;  // (the child slot emits the struct slot's levels: rem stands)
+    lists++;
+    const uint64_t b = (uint64_t)a.offs[d][idx], e = (uint64_t)a.offs[d][idx + 1];
+    if (b == e) return rep | (def << 8);
+    def++;
+    const uint64_t* Cc = a.C[d + 1];
+    const uint64_t t = pre_at(Cc, b) + rem;
+    uint64_t j;
+    if (Cc) {
+      uint64_t lo = b, hi = e;
+      while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (Cc[mid] <= t) lo = mid;
+        else hi = mid;
+      }
+      j = lo;
+    } else {
+      j = t;
+    }
+    if (j != b) rep = lists;
+    rem = t - pre_at(Cc, j);
+    idx = j;
+  }
+  if (a.leaf_nullable && bit_at(a.leaf_valid, idx)) def++;
+  return rep | (def << 8);
+}
+
+__global__ __launch_bounds__(NT) void k_nest_levels(NestLv a) {
+  const uint32_t p = blockIdx.x, tid = threadIdx.x;
+  const uint64_t r0 = (uint64_t)p * a.step;
+  const uint32_t m = (uint32_t)min<uint64_t>(a.step, a.n_rows - r0);
+  const uint64_t k0 = a.lv_at[p];
+  const uint32_t L = (uint32_t)(a.lv_at[p + 1] - k0);
+  const uint64_t h = ((uint64_t)((L + 7) / 8) << 1) | 1;
+  const uint32_t hl = uleb_len(h);
+  const uint32_t rb = a.bw_rep ? (uint32_t)(((uint64_t)L * a.bw_rep + 7) / 8) : 0u;
+  const uint32_t db = a.bw_def ? (uint32_t)(((uint64_t)L * a.bw_def + 7) / 8) : 0u;
+  const uint32_t rlen = a.bw_rep ? hl + rb : 0u, dlen = a.bw_def ? hl + db : 0u;
+  uint8_t* out = a.heads + a.head_at[p];
+  const uint64_t cap = a.head_at[p + 1] - a.head_at[p];
+  if (12ull + rlen + dlen > cap) {  // (the host sizes the slot from the same prefix: not reached)
+    if (tid == 0) a.head_len[p] = ~0u;
+    return;
+  }
+  if (tid == 0) {
+    put8(out, m, 4);
+    put8(out + 4, rlen, 4);
+    put8(out + 8, dlen, 4);
+    for (uint32_t k = 0; k < hl; k++) {
+      const uint8_t c = (uint8_t)((h >> (7 * k)) & 0x7F) | (k + 1 < hl ? 0x80 : 0);
+      if (a.bw_rep) out[12 + k] = c;
+      if (a.bw_def) out[12 + rlen + k] = c;
+    }
+    a.head_len[p] = 12 + rlen + dlen;
+  }
+  uint8_t* rout = out + 12 + hl;
+  uint8_t* dout = out + 12 + rlen + hl;
+  // one 32-level chunk a thread: 4 * bw bytes of each stream; the spare bits of
+  // the last, partial chunk hold level i - 32 (the writer's reused buffer)
+  const uint32_t nch = (L + 31) / 32;
+  for (uint32_t ch = tid; ch < nch; ch += NT) {
+    uint64_t rbits[2] = {0, 0}, dbits[2] = {0, 0};  // 32 levels of <= 4 bits
+    for (uint32_t j = 0; j < 32; j++) {
+      uint32_t i = 32 * ch + j;
+      uint32_t lv = 0;
+      if (i < L || i >= 32) lv = nest_level(a, r0, m, k0 + (i < L ? i : i - 32));
+      const uint64_t r = lv & 0xFF, dd = lv >> 8;
+      const uint32_t qr = j * a.bw_rep, qd = j * a.bw_def;
+      rbits[qr >> 6] |= r << (qr & 63);
+      if ((qr & 63) + a.bw_rep > 64) rbits[1] |= r >> (64 - (qr & 63));
+      dbits[qd >> 6] |= dd << (qd & 63);
+      if ((qd & 63) + a.bw_def > 64) dbits[1] |= dd >> (64 - (qd & 63));
+    }
+    const uint32_t take = min(32u, L - 32 * ch);
+    const uint32_t nr = (take * a.bw_rep + 7) / 8, nd = (take * a.bw_def + 7) / 8;
+    for (uint32_t b = 0; b < nr; b++) rout[(uint64_t)ch * 4 * a.bw_rep + b] = (uint8_t)(rbits[b >> 3] >> (8 * (b & 7)));
+    for (uint32_t b = 0; b < nd; b++) dout[(uint64_t)ch * 4 * a.bw_def + b] = (uint8_t)(dbits[b >> 3] >> (8 * (b & 7)));
+  }
+}
+
 }  // namespace sba
 
 // ===========================================================================
@@ -2054,6 +2238,11 @@ struct ListPart {
   uint64_t head_slot;
   const uint32_t* head_len;
   const uint64_t* h_levels;  // host [np]: PageMeta.num_values
+  // nested pages (encode_nested_device): headers in variable slots, page p's at
+  // heads + head_at[p] (head_slot = the largest); the slices and header slots on the host
+  const uint64_t* head_at = nullptr;    // device [np + 1]
+  const uint64_t* h_rows_at = nullptr;  // host [np + 1]
+  const uint64_t* h_head_at = nullptr;  // host [np + 1]
 };
 
 int encode_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, const uint8_t* d_validity, uint64_t n_rows,
@@ -2083,7 +2272,6 @@ int encode_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, const uint8_
   const bool stats = sba::needs_stats(o, o.forbidden);
   const bool big = P > sba::kMaxRows;
   if (big && (P * w > 0xFFFFFFF0ull || P > 0x7FFFFFFFull)) return SB_E_NYI;
-  if (lp && phys == SB_T_BOOLEAN) return SB_E_NYI;
   const uint64_t slot = adaptive_slot_bytes(P, w, lp ? 0 : nullable) + (lp ? lp->head_slot : 0);
   const uint64_t scr = is_bool ? 256 : ((P > 65535 ? 3 : 2) * P * 8 + 255) & ~255ull;  // (wide: roaring rows, level 2)
   const uint64_t gwb = !big ? 0 : is_bool ? sba::bool_work_bytes(P) : big_work_bytes(P, stats);
@@ -2112,6 +2300,7 @@ int encode_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, const uint8_
       a.heads = lp->heads;
       a.head_slot = lp->head_slot;
       a.head_len = lp->head_len;
+      a.head_at = lp->head_at;
     }
     if (is_bool) {
       if (o.dflt == sba::C_ZSTD) {
@@ -2224,6 +2413,11 @@ __global__ void k_page_offsets(const int64_t* offs, uint64_t n_rows, uint64_t P,
   if (p <= np) out[p] = offs[std::min<uint64_t>(p * P, n_rows)];
 }
 
+__global__ void k_slice_offsets(const int64_t* offs, const uint64_t* rows_at, uint64_t np, int64_t* out) {
+  const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p <= np) out[p] = offs[rows_at[p]];
+}
+
 // per-page slot of a Binary / Utf8 page of n rows and vl value bytes
 static uint64_t binary_slot_bytes(uint64_t n, uint64_t vl, int ow, int nullable) {
   const uint64_t pre = nullable ? 4 + 10 + (n + 7) / 8 : 0;
@@ -2239,7 +2433,7 @@ uint64_t binary_device_bound(uint64_t n_rows, uint64_t values_len, int ow, int n
 int encode_binary_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, uint64_t values_len,
                            const int64_t* d_offsets, const uint8_t* d_validity, uint64_t n_rows, int nullable,
                            const sb_write_options* opts, uint64_t P, uint8_t* d_out, uint64_t out_cap,
-                           uint64_t* out_len, sb_page_meta* h_metas, uint64_t np) {
+                           uint64_t* out_len, sb_page_meta* h_metas, uint64_t np, const ListPart* lp) {
   const int ow = (phys == SB_T_BINARY || phys == SB_T_UTF8) ? 4 : (phys == SB_T_LARGE_BINARY || phys == SB_T_LARGE_UTF8) ? 8 : 0;
   if (!ow) return SB_E_NYI;
   const sba::Opts o{opts->default_codec, opts->has_ratio, opts->ratio, opts->forbidden_mask, opts->forced_codec};
@@ -2255,7 +2449,11 @@ int encode_binary_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, uint6
   int64_t* d_po = (int64_t*)ctx_scratch(ctx, (np + 1) * 8, 3);
   if (!d_po) return ctx_fail(ctx, SB_E_DEVICE, "device encode step 5");
   std::vector<int64_t> po(np + 1);
-  hipLaunchKernelGGL(k_page_offsets, dim3((uint32_t)((np + 256) / 256)), dim3(256), 0, st, d_offsets, n_rows, P, np, d_po);
+  if (lp)  // a nested page's strings: its leaf slice
+    hipLaunchKernelGGL(k_slice_offsets, dim3((uint32_t)((np + 256) / 256)), dim3(256), 0, st, d_offsets, lp->rows_at, np,
+                       d_po);
+  else
+    hipLaunchKernelGGL(k_page_offsets, dim3((uint32_t)((np + 256) / 256)), dim3(256), 0, st, d_offsets, n_rows, P, np, d_po);
   if (hipMemcpyAsync(po.data(), d_po, (np + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
     return ctx_fail(ctx, SB_E_DEVICE, "device encode step 6");
@@ -2264,9 +2462,10 @@ int encode_binary_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, uint6
   std::vector<std::pair<uint64_t, uint64_t>> batches;  // (first page, index of its slot_offs)
   uint64_t acc = 0;
   for (uint64_t p = 0; p < np; p++) {
-    const uint64_t n = std::min<uint64_t>(P, n_rows - p * P);
-    if (po[p + 1] < po[p]) return SB_E_ARG;
-    const uint64_t sb = binary_slot_bytes(n, (uint64_t)(po[p + 1] - po[p]), ow, nullable);
+    const uint64_t n = lp ? lp->h_rows_at[p + 1] - lp->h_rows_at[p] : std::min<uint64_t>(P, n_rows - p * P);
+    if (po[p + 1] < po[p] || po[p] < 0) return SB_E_ARG;
+    const uint64_t sb = binary_slot_bytes(n, (uint64_t)(po[p + 1] - po[p]), ow, lp ? 0 : nullable) +
+                        (lp ? (lp->h_head_at[p + 1] - lp->h_head_at[p] + 15) & ~15ull : 0);
     if (batches.empty() || (acc + sb > (1ull << 30) && p > batches.back().first) || p - batches.back().first >= maxpp) {
       if (!batches.empty()) soff.push_back(acc);
       batches.push_back({p, soff.size()});
@@ -2302,6 +2501,13 @@ int encode_binary_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, uint6
     sba::AdArgs a{d_values, d_validity, n_rows, (uint32_t)P, (uint32_t)b0, (uint32_t)(b1 - b0), nullable, o,
                   opts->seed, slots, 0, scratch, scr, work, gwork, gwb, sizes, status, offs, d_out, out_cap, (uint32_t)np,
                   d_offsets, values_len, ow, d_soff + batches[b].second};
+    if (lp) {
+      a.rows_at = lp->rows_at;
+      a.heads = lp->heads;
+      a.head_slot = lp->head_slot;
+      a.head_len = lp->head_len;
+      a.head_at = lp->head_at;
+    }
     if (ow == 4) launch_bin<4>(a, lds, st);
     else launch_bin<8>(a, lds, st);
     hipLaunchKernelGGL(sba::k_enc_offsets, dim3(1), dim3(sba::NT), 0, st, a);
@@ -2321,11 +2527,244 @@ int encode_binary_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, uint6
     if (stv[p]) return SB_E_OUT_OF_SPEC;
   }
   *out_len = sz[2 * np];
-  for (uint64_t p = 0; p < np; p++) h_metas[p] = sb_page_meta{sz[p], std::min<uint64_t>(P, n_rows - p * P)};
+  for (uint64_t p = 0; p < np; p++)
+    h_metas[p] = sb_page_meta{sz[p], lp ? lp->h_levels[p] : std::min<uint64_t>(P, n_rows - p * P)};
   return SB_OK;
 }
 
+// encode_chunk of one leaf of any nested field on the device (write/common.rs:
+// 60-115, write_nested serialize.rs:135-198): the nests' offsets are checked
+// and their entries counted top-down (one small readback per list nest), the
+// level prefixes are built bottom-up in context scratch, k_nest_levels writes
+// each page's header, and the page's leaf slice goes through the page kernels
+// behind it.  Byte-identical to sb_encode_nested_column.
+static bool is_binary_type(int phys) { return phys >= SB_T_BINARY && phys <= SB_T_LARGE_UTF8; }
+static int enc_type_width(int phys) {
+  switch (phys) {
+    case SB_T_INT8: case SB_T_UINT8: return 1;
+    case SB_T_INT16: case SB_T_UINT16: return 2;
+    case SB_T_INT32: case SB_T_UINT32: case SB_T_FLOAT32: return 4;
+    case SB_T_INT64: case SB_T_UINT64: case SB_T_FLOAT64: return 8;
+  }
+  return 0;
+}
+
+int encode_nested_device(sb_ctx* ctx, const sb_nested_desc* desc, const sb_nest_dev* d_nests, const void* d_values,
+                         const int64_t* d_leaf_offsets, uint64_t values_len, const uint8_t* d_leaf_validity,
+                         uint64_t n_rows, const sb_write_options* opts, uint64_t step, uint8_t* d_out, uint64_t out_cap,
+                         uint64_t* out_len, sb_page_meta* h_metas, uint64_t np) {
+  hipStream_t st = (hipStream_t)sb_ctx_stream(ctx);
+  const int depth = desc->depth, phys = desc->physical_type;
+  const bool binary = is_binary_type(phys);
+  // page metadata in one context slot: check results [2 x (depth + 1)] | lv_at |
+  // rows_at | head_at [np + 1 each] u64 | head_len [np] u32
+  const size_t meta_bytes = 16 * 8 + 3 * (np + 1) * 8 + np * 4;
+  uint64_t* meta = (uint64_t*)ctx_scratch(ctx, meta_bytes, 5);
+  if (!meta) return ctx_fail(ctx, SB_E_DEVICE, "device nested encode alloc");
+  uint64_t* d_res = meta;
+  uint64_t* d_lv_at = meta + 16;
+  uint64_t* d_rows_at = d_lv_at + np + 1;
+  uint64_t* d_head_at = d_rows_at + np + 1;
+  uint32_t* d_hlen = (uint32_t*)(d_head_at + np + 1);
+  // 1. top-down: offsets never decrease; entries per nest
+  uint64_t count[SB_MAX_NEST + 1];
+  count[0] = n_rows;
+  uint64_t res[2];
+  auto check = [&](const int64_t* o, uint64_t cnt, uint64_t* last) -> int {
+    if (hipMemsetAsync(d_res, 0, 16, st) != hipSuccess) return ctx_fail(ctx, SB_E_DEVICE, "device nested encode step 1");
+    hipLaunchKernelGGL(sba::k_nest_check, dim3((uint32_t)(cnt / 256 + 1)), dim3(256), 0, st, o, cnt, d_res);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess)
+      return ctx_fail(ctx, SB_E_DEVICE, "device nested encode launch (step 1)", (int)e);
+    if (hipMemcpyAsync(res, d_res, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+      return ctx_fail(ctx, SB_E_DEVICE, "device nested encode step 1");
+    if (res[0] || (int64_t)res[1] < 0) return ctx_fail(ctx, SB_E_ARG, "decreasing offsets");
+    *last = res[1];
+    return SB_OK;
+  };
+  for (int d = 0; d < depth; d++) {
+    if ((desc->struct_mask >> d) & 1) {
+      count[d + 1] = count[d];
+      continue;
+    }
+    if (count[d] / 256 + 1 > 0x7FFFFFFFull) return SB_E_NYI;
+    if (int rc = check(d_nests[d].d_offsets, count[d], &count[d + 1])) return rc;
+  }
+  const uint64_t n_leaf = count[depth];
+  if (binary) {
+    uint64_t last = 0;
+    if (n_leaf / 256 + 1 > 0x7FFFFFFFull) return SB_E_NYI;
+    if (int rc = check(d_leaf_offsets, n_leaf, &last)) return rc;
+    if (last > values_len) return ctx_fail(ctx, SB_E_ARG, "leaf offsets past the values");
+  }
+  // 2. bottom-up: the level prefixes C_d (nullptr = the identity)
+  const uint64_t* C[SB_MAX_NEST + 1] = {};
+  bool own[SB_MAX_NEST] = {};
+  size_t c_bytes = 0, tmp_bytes = 0;
+  {
+    bool ident = true;  // C_{d + 1} is the identity
+    for (int d = depth - 1; d >= 0; d--) {
+      const bool is_struct = (desc->struct_mask >> d) & 1, nullable = desc->list_nullable[d] != 0;
+      own[d] = is_struct ? (nullable && !ident) : true;
+      if (own[d]) {
+        ident = false;
+        c_bytes += (count[d] + 1) * 8;
+        size_t tb = 0;
+        if (rocprim::exclusive_scan(nullptr, tb, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, count[d] + 1,
+                                    rocprim::plus<uint64_t>(), st) != hipSuccess)
+          return ctx_fail(ctx, SB_E_DEVICE, "device nested encode scan size");
+        tmp_bytes = std::max(tmp_bytes, tb);
+      }
+    }
+  }
+  uint8_t* cbuf = (uint8_t*)ctx_scratch(ctx, c_bytes + tmp_bytes + 256, 7);
+  if (!cbuf) return ctx_fail(ctx, SB_E_DEVICE, "device nested encode alloc");
+  void* d_tmp = cbuf + ((c_bytes + 255) & ~255ull);
+  {
+    uint64_t* at = (uint64_t*)cbuf;
+    for (int d = depth - 1; d >= 0; d--) {
+      const bool is_struct = (desc->struct_mask >> d) & 1;
+      if (!own[d]) {
+        C[d] = C[d + 1];  // a required struct, or one level per slot all the way down
+        continue;
+      }
+      uint64_t* Cd = at;
+      at += count[d] + 1;
+      hipLaunchKernelGGL(sba::k_nest_counts, dim3((uint32_t)(count[d] / 256 + 1)), dim3(256), 0, st,
+                         is_struct ? nullptr : d_nests[d].d_offsets,
+                         desc->list_nullable[d] ? d_nests[d].d_validity : nullptr, C[d + 1], count[d], Cd);
+      size_t tb = tmp_bytes;
+      if (rocprim::exclusive_scan(d_tmp, tb, Cd, Cd, (uint64_t)0, count[d] + 1, rocprim::plus<uint64_t>(), st) !=
+          hipSuccess)
+        return ctx_fail(ctx, SB_E_DEVICE, "device nested encode scan");
+      C[d] = Cd;
+    }
+  }
+  // 3. the page boundaries: level prefix and leaf slot
+  uint32_t max_rep = 0, max_def = desc->item_nullable != 0;
+  sba::NestLv a{};
+  a.depth = depth;
+  a.struct_mask = (uint32_t)desc->struct_mask & ((1u << depth) - 1);
+  a.leaf_nullable = desc->item_nullable != 0;
+  for (int d = 0; d < depth; d++) {
+    const bool is_struct = (a.struct_mask >> d) & 1;
+    if (desc->list_nullable[d]) a.null_mask |= 1u << d;
+    a.offs[d] = is_struct ? nullptr : d_nests[d].d_offsets;
+    a.valid[d] = desc->list_nullable[d] ? d_nests[d].d_validity : nullptr;
+    max_rep += !is_struct;
+    max_def += (desc->list_nullable[d] != 0) + !is_struct;
+  }
+  for (int d = 0; d <= depth; d++) a.C[d] = C[d];
+  a.leaf_valid = d_leaf_validity;
+  a.n_rows = n_rows;
+  a.step = (uint32_t)step;
+  a.bw_rep = max_rep ? 32 - (uint32_t)__builtin_clz(max_rep) : 0;
+  a.bw_def = max_def ? 32 - (uint32_t)__builtin_clz(max_def) : 0;
+  hipLaunchKernelGGL(sba::k_nest_bounds, dim3((uint32_t)(np / 256 + 1)), dim3(256), 0, st, a, np, d_lv_at, d_rows_at);
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess)
+    return ctx_fail(ctx, SB_E_DEVICE, "device nested encode launch (step 3)", (int)e);
+  std::vector<uint64_t> lv_at(np + 1), rows_at(np + 1), head_at(np + 1), levels(np);
+  if (hipMemcpyAsync(lv_at.data(), d_lv_at, (np + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(rows_at.data(), d_rows_at, (np + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return ctx_fail(ctx, SB_E_DEVICE, "device nested encode step 3");
+  uint64_t P = 1, head_max = 0;
+  head_at[0] = 0;
+  for (uint64_t q = 0; q < np; q++) {
+    if (rows_at[q + 1] < rows_at[q] || lv_at[q + 1] < lv_at[q]) return ctx_fail(ctx, SB_E_ARG, "decreasing offsets");
+    P = std::max<uint64_t>(P, rows_at[q + 1] - rows_at[q]);
+    levels[q] = lv_at[q + 1] - lv_at[q];
+    if (levels[q] > 0x3FFFFFFFull) return SB_E_NYI;  // (the stream lengths are u32)
+    // 12 + per stream a ULEB128 run header + the packed levels
+    const uint64_t hb = (12 + 2 * 10 + (levels[q] * a.bw_rep + 7) / 8 + (levels[q] * a.bw_def + 7) / 8 + 15) & ~15ull;
+    head_at[q + 1] = head_at[q] + hb;
+    head_max = std::max(head_max, hb);
+  }
+  uint8_t* d_heads = (uint8_t*)ctx_scratch(ctx, head_at[np] + 16, 6);
+  if (!d_heads) return ctx_fail(ctx, SB_E_DEVICE, "device nested encode alloc");
+  if (hipMemcpyAsync(d_head_at, head_at.data(), (np + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess)
+    return ctx_fail(ctx, SB_E_DEVICE, "device nested encode step 4");
+  a.lv_at = d_lv_at;
+  a.head_at = d_head_at;
+  a.heads = d_heads;
+  a.head_len = d_hlen;
+  hipLaunchKernelGGL(sba::k_nest_levels, dim3((uint32_t)np), dim3(sba::NT), 0, st, a);
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess)
+    return ctx_fail(ctx, SB_E_DEVICE, "device nested encode launch (step 4)", (int)e);
+  // 4. the leaf slices behind their headers (the page encoders synchronize the
+  // stream before they return: head_at outlives its upload)
+  ListPart lp{d_rows_at, d_heads, head_max, d_hlen, levels.data()};
+  lp.head_at = d_head_at;
+  lp.h_rows_at = rows_at.data();
+  lp.h_head_at = head_at.data();
+  const int has_valid = d_leaf_validity != nullptr;  // (feeds the statistics only: no prefix)
+  if (binary)
+    return encode_binary_adaptive(ctx, phys, (const uint8_t*)d_values, values_len, d_leaf_offsets, d_leaf_validity,
+                                  rows_at[np], has_valid, opts, P, d_out, out_cap, out_len, h_metas, np, &lp);
+  return encode_adaptive(ctx, phys, (const uint8_t*)d_values, d_leaf_validity, rows_at[np], has_valid, opts, P, d_out,
+                         out_cap, out_len, h_metas, np, &lp);
+}
+
+uint64_t nested_device_bound(const sb_nested_desc* desc, uint64_t n_rows, uint64_t n_level_bound, uint64_t n_leaf,
+                             uint64_t values_len, uint64_t max_page_rows) {
+  if (!desc) return 0;
+  const uint64_t step = max_page_rows ? std::min(max_page_rows, n_rows) : n_rows;
+  if (!step) return 0;
+  const uint64_t pages = (n_rows + step - 1) / step;
+  const int phys = desc->physical_type;
+  // the headers: 12 + two ULEB128 run headers a page, <= 3 + 4 bits a level, a
+  // page's levels rounded up to bytes per stream
+  const uint64_t heads = pages * (12 + 2 * 10 + 2) + n_level_bound;
+  // the slices: the slot functions are affine in the rows (as
+  // sb_encode_list_device_bound), so the pages' slots sum to <= pages x slot(1) + slot(n_leaf)
+  const uint64_t nl = std::max<uint64_t>(n_leaf, 1);
+  uint64_t body;
+  if (is_binary_type(phys)) {
+    const int ow = (phys == SB_T_BINARY || phys == SB_T_UTF8) ? 4 : 8;
+    body = pages * binary_slot_bytes(1, 0, ow, 0) + binary_slot_bytes(nl, values_len, ow, 0);
+  } else {
+    const uint32_t w = phys == SB_T_BOOLEAN ? 1u : (uint32_t)enc_type_width(phys);
+    if (!w) return 0;
+    body = pages * adaptive_slot_bytes(1, w, 0) + adaptive_slot_bytes(nl, w, 0);
+  }
+  return heads + body + 64;
+}
+
 }  // namespace sb
+
+extern "C" uint64_t sb_encode_nested_device_bound(const sb_nested_desc* desc, uint64_t n_rows, uint64_t n_level_bound,
+                                                  uint64_t n_leaf, uint64_t values_len, uint64_t max_page_rows) {
+  return sb::nested_device_bound(desc, n_rows, n_level_bound, n_leaf, values_len, max_page_rows);
+}
+
+extern "C" sb_status sb_encode_nested_column_device(sb_ctx* ctx, const sb_nested_desc* desc, const sb_nest_dev* d_nests,
+                                                    const void* d_values, const int64_t* d_leaf_offsets,
+                                                    uint64_t values_len, const uint8_t* d_leaf_validity,
+                                                    uint64_t n_rows, const sb_write_options* opts,
+                                                    uint64_t max_page_rows, uint8_t* d_out, uint64_t out_capacity,
+                                                    uint64_t* out_len, sb_page_meta* h_metas, uint64_t metas_cap,
+                                                    uint64_t* n_pages) {
+  if (!ctx || !desc || !d_nests || !opts || !out_len || !n_pages) return SB_E_ARG;
+  const int depth = desc->depth, phys = desc->physical_type;
+  if (depth < 1 || depth > SB_MAX_NEST) return SB_E_NYI;
+  const bool binary = sb::is_binary_type(phys);
+  if (!binary && phys != SB_T_BOOLEAN && !sb::enc_type_width(phys)) return SB_E_NYI;
+  for (int d = 0; d < depth; d++) {
+    if (!((desc->struct_mask >> d) & 1) && !d_nests[d].d_offsets) return SB_E_ARG;
+    if (desc->list_nullable[d] && !d_nests[d].d_validity) return SB_E_ARG;
+  }
+  if ((desc->item_nullable && !d_leaf_validity) || (binary && !d_leaf_offsets) || (n_rows && (!d_out || !d_values)))
+    return SB_E_ARG;
+  const uint64_t step = max_page_rows ? std::min(max_page_rows, n_rows) : n_rows;
+  const uint64_t np = step ? (n_rows + step - 1) / step : 0;
+  *n_pages = np;
+  if (np > metas_cap || (h_metas == nullptr && np)) return SB_E_ARG;
+  *out_len = 0;
+  if (!np) return SB_OK;
+  if (step > sba::kMaxRows) return SB_E_NYI;  // (as sb_encode_list_column_device)
+  if (hipSetDevice(sb_ctx_device(ctx)) != hipSuccess) return (sb_status)sb::ctx_fail(ctx, SB_E_DEVICE, "hipSetDevice");
+  return (sb_status)sb::encode_nested_device(ctx, desc, d_nests, d_values, d_leaf_offsets, values_len, d_leaf_validity,
+                                             n_rows, opts, step, d_out, out_capacity, out_len, h_metas, np);
+}
 
 extern "C" uint64_t sb_encode_binary_device_bound(int32_t physical_type, uint64_t n_rows, uint64_t values_len,
                                                   int32_t nullable, uint64_t max_page_rows) {
@@ -2352,7 +2791,7 @@ extern "C" sb_status sb_encode_binary_column_device(sb_ctx* ctx, int32_t physica
   if (!np) return SB_OK;
   if (hipSetDevice(sb_ctx_device(ctx)) != hipSuccess) return (sb_status)sb::ctx_fail(ctx, SB_E_DEVICE, "hipSetDevice");
   return (sb_status)sb::encode_binary_adaptive(ctx, physical_type, d_values, values_len, d_offsets, d_validity, n_rows,
-                                               nullable, opts, P, d_out, out_capacity, out_len, h_metas, np);
+                                               nullable, opts, P, d_out, out_capacity, out_len, h_metas, np, nullptr);
 }
 
 #ifdef SB_ENC_PHASES

@@ -657,6 +657,246 @@ def encode_field(fld: Field, arr: HostArray, options=None, n_threads: int = 0):
     return out_cols
 
 
+# ---- the device writer: any nested field through sb_encode_nested_column_device
+class NestDevC(ctypes.Structure):
+    _fields_ = [("d_offsets", ctypes.c_void_p), ("d_validity", ctypes.c_void_p)]
+
+
+def _encode_device_lib():
+    L = N.lib()
+    if not getattr(L, "_nested_enc_dev_ready", False):
+        P, U64, I32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32
+        L.sb_encode_nested_device_bound.argtypes = [ctypes.POINTER(NestedDescC), U64, U64, U64, U64, U64]
+        L.sb_encode_nested_device_bound.restype = U64
+        L.sb_encode_nested_column_device.argtypes = [P, ctypes.POINTER(NestedDescC), ctypes.POINTER(NestDevC), P, P, U64, P,
+                                                     U64, ctypes.POINTER(N.WriteOptionsC), U64, P, U64,
+                                                     ctypes.POINTER(U64), ctypes.POINTER(N.PageMetaC), U64,
+                                                     ctypes.POINTER(U64)]
+        L.sb_encode_nested_column_device.restype = I32
+        L._nested_enc_dev_ready = True
+    return L
+
+
+def nested_device_bound(desc: NestedDescC, n_rows: int, n_level_bound: int, n_leaf: int, values_len: int,
+                        max_page_rows: int) -> int:
+    """sb_encode_nested_device_bound: bytes d_out must hold (host only)."""
+    return int(_encode_device_lib().sb_encode_nested_device_bound(ctypes.byref(desc), n_rows, n_level_bound, n_leaf,
+                                                                  values_len, max_page_rows))
+
+
+_BINARY_TYPES = (BINARY, UTF8, LARGE_BINARY, LARGE_UTF8)
+
+
+def device_array(arr: HostArray, device) -> DeviceArray:
+    """A HostArray tree moved to HBM: validities as torch.bool tensors (one
+    per slot), offsets as int64, fixed-width leaves as tensors of their
+    width, Boolean leaves as torch.bool, Binary / Utf8 leaves as (int64
+    offsets, the bytes their slots span)."""
+    import torch
+
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    validity = None if arr.validity is None else up(np.asarray(arr.validity, bool))
+    if arr.kind == "leaf":
+        if isinstance(arr.values, tuple):
+            offs, data = arr.values
+            offs = np.ascontiguousarray(offs, np.int64)
+            end = int(offs[arr.length]) if len(offs) > arr.length else len(data)
+            values = (up(offs), up(np.frombuffer(bytes(data[:end]) or b"\x00", np.uint8).copy()))
+        else:
+            v = np.ascontiguousarray(arr.values)
+            if v.dtype != np.bool_:
+                v = v.view({1: np.uint8, 2: np.int16, 4: np.int32, 8: np.int64}[v.dtype.itemsize])
+            values = up(v)
+        return DeviceArray("leaf", arr.length, validity, values=values)
+    offsets = None if arr.offsets is None else up(np.ascontiguousarray(arr.offsets, np.int64))
+    return DeviceArray(arr.kind, arr.length, validity, offsets, [device_array(c, device) for c in arr.children])
+
+
+def _bad(msg):
+    raise N.StrawboatError(N.E_ARG, msg)
+
+
+def _check_bits(t, n, what):
+    import torch
+
+    if t is None:
+        return
+    if t.dtype == torch.bool:
+        if t.numel() < n:
+            _bad(f"{what}: {t.numel()} validity slots for {n}")
+    elif t.dtype != torch.uint8:
+        _bad(f"{what}: a validity is a torch.bool tensor or a uint8 bitmap")
+    elif t.numel() * 8 < n:
+        _bad(f"{what}: a bitmap of {t.numel()} bytes for {n} slots")
+
+
+def check_device_array(fld: Field, arr: DeviceArray, what: str = "field"):
+    """The buffer lengths of a DeviceArray tree against its slot counts:
+    offsets hold length + 1 entries and end inside the child, struct
+    children hold as many slots as the struct, bitmaps and leaf values cover
+    their slots.  Raises E_ARG on a mismatch."""
+    import torch
+
+    n = arr.length
+    what = f"{what}.{fld.name}" if fld.name else what
+    _check_bits(arr.validity, n, what)
+    if fld.kind == "leaf":
+        v = arr.values
+        if fld.physical_type in _BINARY_TYPES:
+            if not isinstance(v, (tuple, list)) or len(v) != 2:
+                _bad(f"{what}: a Binary / Utf8 leaf is (offsets, bytes)")
+            if v[0].numel() < n + 1:
+                _bad(f"{what}: {v[0].numel()} leaf offsets for {n} slots")
+            if v[1].dtype != torch.uint8:
+                _bad(f"{what}: the bytes of a Binary / Utf8 leaf are uint8")
+            if n and int(v[0][n].item()) > v[1].numel():
+                _bad(f"{what}: leaf offsets end past the bytes")
+        elif fld.physical_type == N.BOOLEAN:
+            _check_bits(v, n, what)
+        else:
+            if v.element_size() != np.dtype(fld.dtype).itemsize:
+                _bad(f"{what}: {v.dtype} values for a {np.dtype(fld.dtype)} leaf")
+            if v.numel() < n:
+                _bad(f"{what}: {v.numel()} values for {n} slots")
+        return
+    if fld.kind == "struct":
+        if len(arr.children) != len(fld.children):
+            _bad(f"{what}: {len(arr.children)} children for {len(fld.children)} fields")
+        for f, c in zip(fld.children, arr.children):
+            if c.length != n:
+                _bad(f"{what}: a struct child of {c.length} slots under {n}")
+            check_device_array(f, c, what)
+        return
+    if arr.offsets is None or arr.offsets.dtype not in (torch.int32, torch.int64):
+        _bad(f"{what}: a list / map holds int32 or int64 offsets")
+    if arr.offsets.numel() < n + 1:
+        _bad(f"{what}: {arr.offsets.numel()} offsets for {n} slots")
+    if len(arr.children) != 1:
+        _bad(f"{what}: a list / map has one child")
+    if n and int(arr.offsets[n].item()) > arr.children[0].length:
+        _bad(f"{what}: offsets end past the child's {arr.children[0].length} slots")
+    check_device_array(fld.children[0], arr.children[0], what)
+
+
+def encode_field_device(fld: Field, arr: DeviceArray, options=None, ctx=None):
+    """encode_field on the GPU (sb_encode_nested_column_device): arr is a
+    DeviceArray tree in HBM -- what FieldDecoder.decode() returns, or
+    device_array(host_array, device).  A validity is a torch.bool tensor per
+    slot (packed here, on the device) or an LSB-first uint8 bitmap, and None
+    under a nullable field reads all-valid, as in encode_field; offsets are
+    int32 or int64; a Binary / Utf8 leaf's values length is the bytes its
+    slots span.  Returns [(device uint8 chunk, [PageMeta])], one per leaf in
+    to_leaves order, byte-identical to encode_field (a Zstd default codec:
+    the device's own frames)."""
+    import torch
+
+    from .write import WriteOptions
+
+    if fld.kind == "leaf":
+        raise N.StrawboatError(N.E_ARG, "a primitive field is not nested: use encode_column_device")
+    paths = fld.leaf_paths()
+    for path in paths:
+        if len(path) - 1 > MAX_NEST:
+            raise N.StrawboatError(N.E_NYI, f"nesting depth {len(path) - 1} not supported")
+        init_chain(path)
+    check_device_array(fld, arr)
+    L = _encode_device_lib()
+    options = options or WriteOptions()
+    opts = options.c()
+
+    def first_tensor(a):
+        for t in (a.validity, a.offsets, a.values[0] if isinstance(a.values, (tuple, list)) else a.values):
+            if t is not None:
+                return t
+        for c in a.children:
+            t = first_tensor(c)
+            if t is not None:
+                return t
+        return None
+
+    ctx = resolve_context(ctx, first_tensor(arr))
+    dev = torch.device("cuda", ctx.device)
+    cache = {}  # per array node: its bitmap and widened offsets, shared by the leaves under it
+
+    def bitmap(t, n, nullable=False):
+        if t is None:
+            if not nullable:
+                return None
+            # a missing bitmap is all-valid, as in encode_field (the C entry point wants the bitmap)
+            if ("ones", n) not in cache:
+                cache[("ones", n)] = torch.full(((n + 7) // 8 or 1,), 255, dtype=torch.uint8, device=dev)
+            return cache[("ones", n)]
+        key = ("b", id(t))
+        if key not in cache:
+            if t.dtype == torch.bool:  # packed on the device, LSB first
+                bits = t.to(dev).reshape(-1)[:n]
+                pad = (-n) % 8
+                if pad:
+                    bits = torch.cat([bits, torch.zeros(pad, dtype=torch.bool, device=dev)])
+                w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=dev)
+                cache[key] = (bits.view(-1, 8).to(torch.uint8) * w).sum(1, dtype=torch.uint8) if n else \
+                    torch.zeros(1, dtype=torch.uint8, device=dev)
+            else:
+                cache[key] = t.to(dev).contiguous() if t.numel() else torch.zeros(1, dtype=torch.uint8, device=dev)
+        return cache[key]
+
+    def wide(t):
+        key = ("o", id(t))
+        if key not in cache:
+            cache[key] = t.to(device=dev, dtype=torch.int64).contiguous()
+        return cache[key]
+
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    n_rows = arr.length
+    P = min(options.max_page_size or n_rows, n_rows)
+    npages = (n_rows + P - 1) // P if n_rows else 0
+    out_cols = []
+    for path in paths:
+        nulls, mask, leaf_null, large = init_chain(path)
+        depth = len(nulls)
+        arrs = _arrays_on_path(arr, path)
+        nests = (NestDevC * MAX_NEST)()
+        keep = []
+        for d in range(depth):
+            a = arrs[d]
+            if not (mask >> d) & 1:
+                o = wide(a.offsets)
+                keep.append(o)
+                nests[d].d_offsets = ptr(o)
+            vb = bitmap(a.validity, a.length, nulls[d])
+            keep.append(vb)
+            nests[d].d_validity = ptr(vb)
+        lf, la = path[-1], arrs[-1]
+        phys = lf.physical_type
+        lo, vlen = None, 0
+        if phys in _BINARY_TYPES:
+            lo = wide(la.values[0])
+            vals = la.values[1].to(dev).contiguous()
+            vlen = int(lo[la.length].item()) if la.length else 0
+        elif phys == N.BOOLEAN:
+            vals = bitmap(la.values, la.length)
+        else:
+            vals = la.values.to(dev).contiguous()
+        if vals.numel() == 0:
+            vals = torch.zeros(1, dtype=vals.dtype, device=dev)
+        lvb = bitmap(la.validity, la.length, leaf_null)
+        ln = (ctypes.c_int32 * MAX_NEST)(*([int(x) for x in nulls] + [0] * (MAX_NEST - depth)))
+        desc = NestedDescC(phys, depth, ln, int(leaf_null), 8 if large else 4, mask)
+        n_level_bound = sum(a.length for a in arrs)
+        cap = nested_device_bound(desc, n_rows, n_level_bound, la.length, vlen, P)
+        out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+        metas = (N.PageMetaC * max(npages, 1))()
+        olen, npg = ctypes.c_uint64(), ctypes.c_uint64()
+        st = L.sb_encode_nested_column_device(ctx._h, ctypes.byref(desc), nests, ptr(vals), ptr(lo), vlen, ptr(lvb),
+                                              n_rows, ctypes.byref(opts), P, ptr(out), out.numel(), ctypes.byref(olen),
+                                              metas, max(npages, 1), ctypes.byref(npg))
+        if st:
+            raise N.StrawboatError(st, "encode_nested_column_device: " + ctx.error())
+        out_cols.append((out[: olen.value], [PageMeta(metas[i].length, metas[i].num_values) for i in range(npg.value)]))
+    return out_cols
+
+
 def batch_read_field(fld: Field, columns, ctx: Optional[Context] = None) -> DeviceArray:
     """batch_read_array for a nested field (List / Map / Struct trees):
     columns = one (chunk, page metas) per leaf, to_leaves order."""

@@ -281,17 +281,21 @@ class NativeWriter:
         """columns: one entry per field of the chunk, equal lengths -- a flat
         field as (values, validity|None, nullable), a Binary / Utf8 field as
         (BinaryColumn-like (offsets, bytes) values, validity|None, nullable,
-        physical type), a nested field as (pa_amd.Field, pa_amd.HostArray):
-        encode_chunk writes every leaf of it, to_leaves order
-        (write/common.rs:60-115)."""
-        from .nested import Field, encode_field
+        physical type), a nested field as (pa_amd.Field, pa_amd.HostArray)
+        or, for a field in HBM, (pa_amd.Field, pa_amd.DeviceArray), which the
+        device writer encodes (encode_field_device): encode_chunk writes
+        every leaf of it, to_leaves order (write/common.rs:60-115)."""
+        from .nested import DeviceArray, Field, encode_field, encode_field_device
 
         if self.state == "written":
             raise N.StrawboatError(N.E_OUT_OF_SPEC, "The strawboat file can only accept one RowGroup in a single file")
         if self.state != "started":
             raise N.StrawboatError(N.E_OUT_OF_SPEC, "The strawboat file must be started before it can be written to")
         for col in columns:
-            if isinstance(col[0], Field):
+            if isinstance(col[0], Field) and isinstance(col[1], DeviceArray):  # a field in HBM: the device writer
+                leaves = [(bytes(c.cpu().numpy().tobytes()), pm)
+                          for c, pm in encode_field_device(col[0], col[1], self.options)]
+            elif isinstance(col[0], Field):
                 leaves = encode_field(col[0], col[1], self.options)
             elif len(col) == 4:
                 from .binary import encode_binary_column

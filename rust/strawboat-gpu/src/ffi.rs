@@ -51,6 +51,9 @@ pub struct sb_nested_out { pub d_offsets: [*mut c_void; 4], pub d_validity: [*mu
 pub struct sb_nest_in { pub h_offsets: *const i64, pub h_validity: *const u8 }
 
 #[repr(C)] #[derive(Clone, Copy)]
+pub struct sb_nest_dev { pub d_offsets: *const i64, pub d_validity: *const u8 }
+
+#[repr(C)] #[derive(Clone, Copy)]
 pub struct sb_write_options {
     pub default_codec: i32, pub has_ratio: i32, pub ratio: f64,
     pub forbidden_mask: u32, pub forced_codec: i32, pub seed: u64,
@@ -129,6 +132,13 @@ extern "C" {
                                         opts: *const sb_write_options, max_page_rows: u64, d_out: *mut u8,
                                         out_capacity: u64, out_len: *mut u64, metas: *mut sb_page_meta,
                                         metas_cap: u64, n_pages: *mut u64) -> i32;
+    pub fn sb_encode_nested_device_bound(desc: *const sb_nested_desc, n_rows: u64, n_level_bound: u64, n_leaf: u64,
+                                         values_len: u64, max_page_rows: u64) -> u64;
+    pub fn sb_encode_nested_column_device(ctx: *mut sb_ctx, desc: *const sb_nested_desc, d_nests: *const sb_nest_dev,
+                                          d_values: *const c_void, d_leaf_offsets: *const i64, values_len: u64,
+                                          d_leaf_validity: *const u8, n_rows: u64, opts: *const sb_write_options,
+                                          max_page_rows: u64, d_out: *mut u8, out_capacity: u64, out_len: *mut u64,
+                                          metas: *mut sb_page_meta, metas_cap: u64, n_pages: *mut u64) -> i32;
     pub fn sb_encode_page(physical_type: i32, values: *const c_void, validity: *const u8, n: u64,
                           nullable: i32, opts: *const sb_write_options, seed: u64, out: *mut *mut u8,
                           out_len: *mut u64) -> i32;

@@ -695,6 +695,78 @@ pub fn encode_column_device(ctx: &Context, ty: PhysicalType, values: &DeviceBuff
     Ok((out, metas))
 }
 
+/// One nest of a leaf path in HBM for [`encode_nested_column_device`]: a List /
+/// Map nest brings its `entries + 1` absolute int64 offsets, a nullable nest
+/// its LSB validity bitmap; `entries` is the nest's slot count.
+pub struct DeviceNest<'a> {
+    pub offsets: Option<&'a DeviceBuffer>,
+    pub validity: Option<&'a DeviceBuffer>,
+    pub nullable: bool,
+    pub is_struct: bool,
+    pub entries: u64,
+}
+
+/// The leaf of a nested path in HBM: `values` holds its slots (Boolean: their
+/// LSB bitmap; Binary / Utf8: the bytes, `values_len` of them, with
+/// `offsets` = slots + 1 absolute int64 positions).
+pub struct DeviceLeaf<'a> {
+    pub ty: PhysicalType,
+    pub values: &'a DeviceBuffer,
+    pub offsets: Option<&'a DeviceBuffer>,
+    pub values_len: u64,
+    pub validity: Option<&'a DeviceBuffer>,
+    pub nullable: bool,
+    pub slots: u64,
+}
+
+/// `encode_chunk` of one leaf column of any nested field on the device
+/// (sb_encode_nested_column_device): nests outermost first, every buffer in
+/// HBM -> the column chunk in HBM + its page metas (num_values = the page's
+/// level count).
+pub fn encode_nested_column_device(ctx: &Context, nests: &[DeviceNest], leaf: &DeviceLeaf, n_rows: u64,
+                                   opts: &WriteOptions) -> Result<(DeviceBuffer, Vec<PageMeta>)> {
+    if nests.is_empty() || nests.len() > ffi::SB_MAX_NEST {
+        return Err(Error::NotYetImplemented(format!("{} nests", nests.len())));
+    }
+    let mut desc = ffi::sb_nested_desc {
+        physical_type: leaf.ty as i32,
+        depth: nests.len() as i32,
+        list_nullable: [0; 4],
+        item_nullable: leaf.nullable as i32,
+        offset_width: 4,
+        struct_mask: 0,
+    };
+    let mut raw = [ffi::sb_nest_dev { d_offsets: ptr::null(), d_validity: ptr::null() }; ffi::SB_MAX_NEST];
+    let mut level_bound = leaf.slots;
+    for (d, n) in nests.iter().enumerate() {
+        desc.list_nullable[d] = n.nullable as i32;
+        if n.is_struct {
+            desc.struct_mask |= 1 << d;
+        }
+        raw[d].d_offsets = n.offsets.map_or(ptr::null(), |b| b.ptr as *const i64);
+        raw[d].d_validity = n.validity.map_or(ptr::null(), |b| b.ptr as *const u8);
+        level_bound += n.entries;
+    }
+    let page = opts.max_page_size.unwrap_or(0);
+    let cap = unsafe {
+        ffi::sb_encode_nested_device_bound(&desc, n_rows, level_bound, leaf.slots, leaf.values_len, page)
+    };
+    let out = ctx.alloc(cap.max(16) as usize)?;
+    let p = opts.max_page_size.unwrap_or(n_rows).min(n_rows).max(1);
+    let mut metas = vec![PageMeta { length: 0, num_values: 0 }; ((n_rows + p - 1) / p).max(1) as usize];
+    let (mut len, mut np) = (0u64, 0u64);
+    let o = opts.raw();
+    status(unsafe {
+        ffi::sb_encode_nested_column_device(ctx.raw, &desc, raw.as_ptr(), leaf.values.ptr as *const c_void,
+                                            leaf.offsets.map_or(ptr::null(), |b| b.ptr as *const i64), leaf.values_len,
+                                            leaf.validity.map_or(ptr::null(), |b| b.ptr as *const u8), n_rows, &o, page,
+                                            out.ptr as *mut u8, cap.max(16), &mut len, metas.as_mut_ptr(),
+                                            metas.len() as u64, &mut np)
+    }, || ctx.last_error())?;
+    metas.truncate(np as usize);
+    Ok((out, metas))
+}
+
 /// `NativeWriter::finish` footer bytes for the given column metas.
 pub fn write_footer(schema: &[u8], columns: &[ColumnMeta]) -> Result<Vec<u8>> {
     let offs: Vec<u64> = columns.iter().map(|c| c.offset).collect();
