@@ -90,7 +90,7 @@ def encode_binary_column_device(values, offsets, validity=None, nullable: bool =
     chunk, page metas), byte-identical to encode_binary_column."""
     import torch
 
-    from .write import WriteOptions
+    from .write import WriteOptions, pack_bits, page_rows, run_device_encode
 
     L = _lib()
     options = options or WriteOptions()
@@ -98,30 +98,19 @@ def encode_binary_column_device(values, offsets, validity=None, nullable: bool =
     offsets = offsets.to(dtype=torch.int64).contiguous()
     values = values.contiguous()
     n = offsets.numel() - 1
+    dev = offsets.device
     vb = None
     if nullable:
-        v = (validity.to(device=offsets.device, dtype=torch.bool).reshape(-1) if validity is not None
-             else torch.ones(n, dtype=torch.bool, device=offsets.device))
-        pad = (-n) % 8
-        if pad:
-            v = torch.cat([v, torch.zeros(pad, dtype=torch.bool, device=v.device)])
-        w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=v.device)
-        vb = (v.view(-1, 8).to(torch.uint8) * w).sum(1, dtype=torch.uint8) if n else torch.zeros(
-            1, dtype=torch.uint8, device=v.device)
-    P = min(options.max_page_size or n, n)
-    cap = L.sb_encode_binary_device_bound(physical_type, n, values.numel(), int(nullable), P)
-    out = torch.empty(max(cap, 16), dtype=torch.uint8, device=offsets.device)
-    npages = (n + P - 1) // P if n else 0
-    metas = (N.PageMetaC * max(npages, 1))()
-    olen, npg = ctypes.c_uint64(), ctypes.c_uint64()
+        vb = pack_bits(validity if validity is not None else torch.ones(n, dtype=torch.bool, device=dev), n, dev)
+    P, npages = page_rows(options, n)
     opts = options.c()
-    st = L.sb_encode_binary_column_device(
-        ctx._h, physical_type, ctypes.c_void_p(values.data_ptr()), values.numel(), ctypes.c_void_p(offsets.data_ptr()),
-        None if vb is None else ctypes.c_void_p(vb.data_ptr()), n, int(nullable), ctypes.byref(opts), P,
-        ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.byref(olen), metas, max(npages, 1), ctypes.byref(npg))
-    if st:
-        raise N.StrawboatError(st, "encode_binary_column_device: " + ctx.error())
-    return out[: olen.value], [PageMeta(metas[i].length, metas[i].num_values) for i in range(npg.value)]
+    return run_device_encode(
+        "encode_binary_column_device", ctx, dev,
+        L.sb_encode_binary_device_bound(physical_type, n, values.numel(), int(nullable), P), npages,
+        lambda *out: L.sb_encode_binary_column_device(
+            ctx._h, physical_type, ctypes.c_void_p(values.data_ptr()), values.numel(),
+            ctypes.c_void_p(offsets.data_ptr()), None if vb is None else ctypes.c_void_p(vb.data_ptr()), n,
+            int(nullable), ctypes.byref(opts), P, *out))
 
 
 class BinaryColumnDecoder:

@@ -41,12 +41,14 @@
 #include <algorithm>
 #include <vector>
 
-#include "../../include/strawboat_gpu.h"
-#include "sb_internal.h"
+#include "sb_encode_dev.h"
 #include "sb_lz4c.h"
 #include "sb_zstdc.h"
 
 namespace sba {
+
+using sb::put_uleb;
+using sb::uleb_len;
 
 #ifndef SB_ENC_NT
 #define SB_ENC_NT 256
@@ -1128,14 +1130,13 @@ struct AdArgs {
   uint64_t parent_len;      // the array's whole values length (stats and the Extend header)
   int ow;                   // offset width 4 / 8
   const uint64_t* slot_offs;  // per page of the batch: slot start (variable slots), [n_batch] = end
-  // List values (sb_encode_list_column_device): page p holds the child values
-  // [rows_at[p], rows_at[p + 1]) and starts with its level header (heads + p *
-  // head_slot, head_len[p] bytes) in place of a validity prefix
-  const uint64_t* rows_at = nullptr;
-  const uint8_t* heads = nullptr;
-  uint64_t head_slot = 0;
-  const uint32_t* head_len = nullptr;
-  const uint64_t* head_at = nullptr;  // nested pages: page p's header at heads + head_at[p] (variable slots)
+  // List and nested pages (sb::ListPart): page p holds the leaf values
+  // [rows_at[p], rows_at[p + 1]) and starts with its level header (heads +
+  // head_at[p], head_len[p] bytes) in place of a validity prefix; else all null
+  const uint64_t* rows_at;
+  const uint64_t* head_at;
+  const uint8_t* heads;
+  const uint32_t* head_len;
 };
 
 // Page p's rows: [p * P, min((p + 1) * P, n_rows)), or a List page's child values
@@ -1152,9 +1153,9 @@ __device__ __forceinline__ void page_rows(const AdArgs& A, uint32_t p, uint64_t*
 // A List page's level header, copied to the page's start by the threads of
 // `nt`; returns its length
 __device__ __forceinline__ uint32_t put_head(const AdArgs& A, uint32_t p, uint8_t* out, uint32_t nt) {
-  const uint64_t hcap = A.head_at ? A.head_at[p + 1] - A.head_at[p] : A.head_slot;
-  const uint32_t hl = (uint32_t)min<uint64_t>(A.head_len[p], hcap);  // never past the header's slot
-  const uint8_t* h = A.heads + (A.head_at ? A.head_at[p] : (uint64_t)p * A.head_slot);
+  const uint64_t at = A.head_at[p];
+  const uint32_t hl = (uint32_t)min<uint64_t>(A.head_len[p], A.head_at[p + 1] - at);  // never past the header's slot
+  const uint8_t* h = A.heads + at;
   for (uint32_t j = threadIdx.x; j < hl; j += nt) out[j] = h[j];
   return hl;
 }
@@ -1171,15 +1172,6 @@ __device__ __forceinline__ uint64_t page_seed(uint64_t seed, uint64_t page) {  /
   return rng_next(s);
 }
 
-__device__ __forceinline__ uint32_t uleb_len(uint64_t h) {
-  uint32_t l = 1;
-  while (h >= 0x80) {
-    h >>= 7;
-    l++;
-  }
-  return l;
-}
-
 // write_validity (serialize.rs:200-215): u32 def_len + ULEB128 bit-packed run
 // header + the page's validity bitmap; returns its length (0 when not nullable).
 __device__ uint32_t write_prefix(Ctx& c, const AdArgs& A, uint64_t r0, uint32_t n) {
@@ -1187,11 +1179,11 @@ __device__ uint32_t write_prefix(Ctx& c, const AdArgs& A, uint64_t r0, uint32_t 
   const uint32_t tid = threadIdx.x;
   const bool has_vb = A.validity != nullptr;
   const uint32_t nb = (n + 7) / 8;
-  uint64_t h = ((uint64_t)nb << 1) | 1;
+  const uint64_t h = ((uint64_t)nb << 1) | 1;
   const uint32_t hl = uleb_len(h);
   if (tid == 0) {
     put8(c.out, hl + nb, 4);
-    for (uint32_t j = 0; j < hl; j++, h >>= 7) c.out[4 + j] = (uint8_t)((h & 0x7F) | (j + 1 < hl ? 0x80 : 0));
+    put_uleb(c.out + 4, h);
   }
   for (uint32_t j = tid; j < nb; j += NT) {
     uint32_t v = 0;
@@ -1393,14 +1385,14 @@ __global__ __launch_bounds__(64) void k_enc_basic_wave(AdArgs A) {
     __threadfence_block();
   } else if (A.nullable) {  // write_prefix (serialize.rs:200-215), one wave
     const uint32_t nb = (n + 7) / 8;
-    uint64_t h = ((uint64_t)nb << 1) | 1;
+    const uint64_t h = ((uint64_t)nb << 1) | 1;
     const uint32_t hl = uleb_len(h);
     if (4 + hl + nb > cap) {
       err = E_CAP;
     } else {
       if (lane == 0) {
         put8(out, hl + nb, 4);
-        for (uint32_t j = 0; j < hl; j++, h >>= 7) out[4 + j] = (uint8_t)((h & 0x7F) | (j + 1 < hl ? 0x80 : 0));
+        put_uleb(out + 4, h);
       }
       for (uint32_t j = lane; j < nb; j += 64) {
         uint32_t v = 0;
@@ -1930,19 +1922,15 @@ __global__ __launch_bounds__(NT) void k_enc_list_levels(ListLv a) {
     const uint32_t def = a.ni ? (!a.cvalid || bit_at(a.cvalid, (uint64_t)b + j) ? max_def : max_def - 1) : max_def;
     return (j > 0 ? 1u : 0u) | (def << 1);
   };
-  uint64_t h = ((uint64_t)((L + 7) / 8) << 1) | 1;
-  uint32_t hl = 1;
-  for (uint64_t t = h; t >= 0x80; t >>= 7) hl++;
+  const uint64_t h = ((uint64_t)((L + 7) / 8) << 1) | 1;
+  const uint32_t hl = uleb_len(h);
   const uint32_t rb = (L + 7) / 8, db = (L * bwd + 7) / 8;
   uint8_t* out = a.heads + (uint64_t)p * a.head_slot;
   if (tid == 0) {
     const uint32_t w[3] = {m, hl + rb, hl + db};
     for (uint32_t k = 0; k < 12; k++) out[k] = (uint8_t)(w[k / 4] >> (8 * (k % 4)));
-    for (uint32_t k = 0; k < hl; k++) {
-      const uint8_t c = (uint8_t)((h >> (7 * k)) & 0x7F) | (k + 1 < hl ? 0x80 : 0);
-      out[12 + k] = c;
-      out[12 + hl + rb + k] = c;
-    }
+    put_uleb(out + 12, h);
+    put_uleb(out + 12 + hl + rb, h);
     a.head_len[p] = 12 + 2 * hl + rb + db;
     a.levels[p] = L;
   }
@@ -2100,11 +2088,8 @@ __global__ __launch_bounds__(NT) void k_nest_levels(NestLv a) {
     put8(out, m, 4);
     put8(out + 4, rlen, 4);
     put8(out + 8, dlen, 4);
-    for (uint32_t k = 0; k < hl; k++) {
-      const uint8_t c = (uint8_t)((h >> (7 * k)) & 0x7F) | (k + 1 < hl ? 0x80 : 0);
-      if (a.bw_rep) out[12 + k] = c;
-      if (a.bw_def) out[12 + rlen + k] = c;
-    }
+    if (a.bw_rep) put_uleb(out + 12, h);
+    if (a.bw_def) put_uleb(out + 12 + rlen, h);
     a.head_len[p] = 12 + rlen + dlen;
   }
   uint8_t* rout = out + 12 + hl;
@@ -2215,6 +2200,7 @@ static void launch_t(const sba::AdArgs& a, uint32_t lds, hipStream_t st) {
     hipLaunchKernelGGL((sba::k_enc_adaptive<W, FLT, SGN, false>), dim3(a.n_batch), dim3(sba::NT), lds, st, a);
   }
 }
+constexpr uint32_t type_key(uint32_t w, bool flt, bool sgn) { return w | (flt ? 16u : 0u) | (sgn ? 32u : 0u); }
 template <int OW>
 static void launch_bin(const sba::AdArgs& a, uint32_t lds, hipStream_t st) {
   if (wave_basic(a.o)) {
@@ -2230,49 +2216,75 @@ static void launch_bin(const sba::AdArgs& a, uint32_t lds, hipStream_t st) {
   }
 }
 
-// Encodes every page of a fixed-width column; returns SB status.
-// List pages (encode_list_device): each page's child-value range and level header
-struct ListPart {
-  const uint64_t* rows_at;  // device [np + 1]
-  const uint8_t* heads;
-  uint64_t head_slot;
-  const uint32_t* head_len;
-  const uint64_t* h_levels;  // host [np]: PageMeta.num_values
-  // nested pages (encode_nested_device): headers in variable slots, page p's at
-  // heads + head_at[p] (head_slot = the largest); the slices and header slots on the host
-  const uint64_t* head_at = nullptr;    // device [np + 1]
-  const uint64_t* h_rows_at = nullptr;  // host [np + 1]
-  const uint64_t* h_head_at = nullptr;  // host [np + 1]
-};
+sb_status begin_pages(sb_ctx* ctx, const PagePlan& pl, uint64_t max_step, sb_page_meta* h_metas, uint64_t metas_cap,
+                      uint64_t* n_pages, uint64_t* out_len) {
+  *n_pages = pl.np;
+  if (pl.np > metas_cap || (h_metas == nullptr && pl.np)) return SB_E_ARG;
+  *out_len = 0;
+  if (!pl.np) return SB_OK;
+  if (pl.step > max_step) return SB_E_NYI;
+  if (hipSetDevice(sb_ctx_device(ctx)) != hipSuccess) return (sb_status)ctx_fail(ctx, SB_E_DEVICE, "hipSetDevice");
+  return SB_OK;
+}
 
+// A page kernel's arguments for leaf slices behind level headers
+static void set_pages(sba::AdArgs& a, const ListPart* lp) {
+  if (!lp) return;
+  a.rows_at = lp->rows_at;
+  a.head_at = lp->head_at;
+  a.heads = lp->heads;
+  a.head_len = lp->head_len;
+}
+
+// After a batch's page kernel: its pages' offsets in the output, then slot -> output
+static int place_batch(sb_ctx* ctx, const sba::AdArgs& a, hipStream_t st, const char* what) {
+  hipLaunchKernelGGL(sba::k_enc_offsets, dim3(1), dim3(sba::NT), 0, st, a);
+  hipLaunchKernelGGL(sba::k_enc_compact, dim3(a.n_batch), dim3(sba::NT), 0, st, a);
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return ctx_fail(ctx, SB_E_DEVICE, what, (int)e);
+  return SB_OK;
+}
+
+// After the last batch: sizes [np] | offs [np + 1] and the pages' status come
+// back, the first failed page decides the status, else the chunk length and
+// the page metas are filled.
+static int finish_pages(sb_ctx* ctx, hipStream_t st, const uint64_t* sizes, const uint32_t* status, uint64_t np,
+                        uint64_t P, uint64_t n_rows, const ListPart* lp, uint64_t* out_len, sb_page_meta* h_metas,
+                        const char* what) {
+  std::vector<uint64_t> sz(2 * np + 1);
+  std::vector<uint32_t> stv(np);
+  if (hipMemcpyAsync(sz.data(), sizes, (2 * np + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(stv.data(), status, np * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return ctx_fail(ctx, SB_E_DEVICE, what);
+  for (uint64_t p = 0; p < np; p++) {
+    if (stv[p] == sba::E_NYI) return SB_E_NYI;
+    if (stv[p] == sba::E_CAP) return SB_E_ARG;
+    if (stv[p]) return SB_E_OUT_OF_SPEC;
+  }
+  *out_len = sz[2 * np];
+  for (uint64_t p = 0; p < np; p++)
+    h_metas[p] = sb_page_meta{sz[p], lp ? lp->h_levels[p] : std::min<uint64_t>(P, n_rows - p * P)};
+  return SB_OK;
+}
+
+// Encodes every page of a fixed-width column; returns SB status.
 int encode_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, const uint8_t* d_validity, uint64_t n_rows,
                     int nullable, const sb_write_options* opts, uint64_t P, uint8_t* d_out, uint64_t out_cap,
                     uint64_t* out_len, sb_page_meta* h_metas, uint64_t np, const ListPart* lp) {
   sba::Opts o{opts->default_codec, opts->has_ratio, opts->ratio, opts->forbidden_mask, opts->forced_codec};
-  uint32_t w = 0;
-  bool flt = false, sgn = false;
-  switch (phys) {
-    case SB_T_INT8: w = 1; sgn = true; break;
-    case SB_T_INT16: w = 2; sgn = true; break;
-    case SB_T_INT32: w = 4; sgn = true; break;
-    case SB_T_INT64: w = 8; sgn = true; break;
-    case SB_T_UINT8: w = 1; break;
-    case SB_T_UINT16: w = 2; break;
-    case SB_T_UINT32: w = 4; break;
-    case SB_T_UINT64: w = 8; break;
-    case SB_T_FLOAT32: w = 4; flt = true; break;
-    case SB_T_FLOAT64: w = 8; flt = true; break;
-    case SB_T_BOOLEAN: w = 1; break;
-    default: return SB_E_NYI;
-  }
-  const bool is_bool = phys == SB_T_BOOLEAN;
+  const EncType t = enc_type(phys);
+  const uint32_t w = t.width;
+  const bool is_bool = t.is_bool;
+  if (!w) return SB_E_NYI;
   // Pages over kMaxRows rows keep their work area in HBM (any size; over
   // 65535 rows with 64-bit table words and several roaring containers);
   // Boolean pages stage their bits in LDS up to kMaxRows, in HBM past it
   const bool stats = sba::needs_stats(o, o.forbidden);
   const bool big = P > sba::kMaxRows;
   if (big && (P * w > 0xFFFFFFF0ull || P > 0x7FFFFFFFull)) return SB_E_NYI;
-  const uint64_t slot = adaptive_slot_bytes(P, w, lp ? 0 : nullable) + (lp ? lp->head_slot : 0);
+  uint64_t head_max = 0;  // (a leaf slice's slot: its header's, then the values')
+  for (uint64_t p = 0; lp && p < np; p++) head_max = std::max(head_max, lp->h_head_at[p + 1] - lp->h_head_at[p]);
+  const uint64_t slot = adaptive_slot_bytes(P, w, lp ? 0 : nullable) + head_max;
   const uint64_t scr = is_bool ? 256 : ((P > 65535 ? 3 : 2) * P * 8 + 255) & ~255ull;  // (wide: roaring rows, level 2)
   const uint64_t gwb = !big ? 0 : is_bool ? sba::bool_work_bytes(P) : big_work_bytes(P, stats);
   const uint32_t batch = batch_pages(np, slot + scr + gwb);
@@ -2295,13 +2307,7 @@ int encode_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, const uint8_
     sba::AdArgs a{d_values, d_validity, n_rows, (uint32_t)P, (uint32_t)b0, (uint32_t)std::min<uint64_t>(batch, np - b0),
                   nullable, o, opts->seed, slots, slot, scratch, scr, work, gwork, gwb, sizes, status, offs, d_out, out_cap,
                   (uint32_t)np, nullptr, 0, 0, nullptr};
-    if (lp) {
-      a.rows_at = lp->rows_at;
-      a.heads = lp->heads;
-      a.head_slot = lp->head_slot;
-      a.head_len = lp->head_len;
-      a.head_at = lp->head_at;
-    }
+    set_pages(a, lp);
     if (is_bool) {
       if (o.dflt == sba::C_ZSTD) {
         ensure_lds_attr(sba::k_enc_bool<true>, (int)lds);
@@ -2310,40 +2316,18 @@ int encode_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, const uint8_
         ensure_lds_attr(sba::k_enc_bool<false>, (int)lds);
         hipLaunchKernelGGL(sba::k_enc_bool<false>, dim3(a.n_batch), dim3(sba::NT), lds, st, a);
       }
-    } else if (flt) {
-      if (w == 4) launch_t<4, true, false>(a, lds, st);
-      else launch_t<8, true, false>(a, lds, st);
-    } else if (sgn) {
-      if (w == 1) launch_t<1, false, true>(a, lds, st);
-      else if (w == 2) launch_t<2, false, true>(a, lds, st);
-      else if (w == 4) launch_t<4, false, true>(a, lds, st);
-      else launch_t<8, false, true>(a, lds, st);
     } else {
-      if (w == 1) launch_t<1, false, false>(a, lds, st);
-      else if (w == 2) launch_t<2, false, false>(a, lds, st);
-      else if (w == 4) launch_t<4, false, false>(a, lds, st);
-      else launch_t<8, false, false>(a, lds, st);
+      switch (type_key(t.width, t.is_float, t.is_signed)) {  // the ten <W, FLT, SGN> of enc_type's numbers
+#define LT(W, FLT, SGN) case type_key(W, FLT, SGN): launch_t<W, FLT, SGN>(a, lds, st); break;
+        LT(1, false, true) LT(2, false, true) LT(4, false, true) LT(8, false, true)
+        LT(1, false, false) LT(2, false, false) LT(4, false, false) LT(8, false, false)
+        LT(4, true, false) LT(8, true, false)
+#undef LT
+      }
     }
-    hipLaunchKernelGGL(sba::k_enc_offsets, dim3(1), dim3(sba::NT), 0, st, a);
-    hipLaunchKernelGGL(sba::k_enc_compact, dim3(a.n_batch), dim3(sba::NT), 0, st, a);
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess)
-      return ctx_fail(ctx, SB_E_DEVICE, "device encode launch (step 3)", (int)e);
+    if (int rc = place_batch(ctx, a, st, "device encode launch (step 3)")) return rc;
   }
-  std::vector<uint64_t> sz(np + 1 + np);
-  std::vector<uint32_t> stv(np);
-  if (hipMemcpyAsync(sz.data(), sizes, (2 * np + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(stv.data(), status, np * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    return ctx_fail(ctx, SB_E_DEVICE, "device encode step 4");
-  for (uint64_t p = 0; p < np; p++) {
-    if (stv[p] == sba::E_NYI) return SB_E_NYI;
-    if (stv[p] == sba::E_CAP) return SB_E_ARG;
-    if (stv[p]) return SB_E_OUT_OF_SPEC;
-  }
-  *out_len = sz[np + np];
-  for (uint64_t p = 0; p < np; p++)
-    h_metas[p] = sb_page_meta{sz[p], lp ? lp->h_levels[p] : std::min<uint64_t>(P, n_rows - p * P)};
-  return SB_OK;
+  return finish_pages(ctx, st, sizes, status, np, P, n_rows, lp, out_len, h_metas, "device encode step 4");
 }
 
 // encode_chunk of one List<primitive> leaf on the device (write/common.rs:
@@ -2357,21 +2341,26 @@ __global__ void k_list_rows_at(const int64_t* offs, uint64_t n_rows, uint64_t st
   const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p <= np) out[p] = (uint64_t)offs[std::min<uint64_t>(p * step, n_rows)];
 }
+__global__ void k_list_head_at(uint64_t head_slot, uint64_t np, uint64_t* out) {  // uniform header slots
+  const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p <= np) out[p] = p * head_slot;
+}
 
 int encode_list_device(sb_ctx* ctx, int phys, const int64_t* d_offsets, const uint8_t* d_list_validity,
                        int list_nullable, const void* d_child, const uint8_t* d_child_validity, int item_nullable,
                        uint64_t n_rows, const sb_write_options* opts, uint64_t step, uint8_t* d_out, uint64_t out_cap,
                        uint64_t* out_len, sb_page_meta* h_metas, uint64_t np) {
   hipStream_t st = (hipStream_t)sb_ctx_stream(ctx);
-  // rows_at [np + 1] u64 | levels [np] u64 | head_len [np] u32 in one grow-only
-  // context slot, the page headers in another (encode_adaptive uses 0..4)
-  const size_t meta_bytes = (np + 1) * 8 + np * 8 + np * 4;
+  // rows_at | head_at [np + 1 each] u64 | levels [np] u64 | head_len [np] u32 in one
+  // grow-only context slot, the page headers in another (encode_adaptive uses 0..4)
+  const size_t meta_bytes = 2 * (np + 1) * 8 + np * 8 + np * 4;
   uint8_t* meta = (uint8_t*)ctx_scratch(ctx, meta_bytes, 5);
   if (!meta) return ctx_fail(ctx, SB_E_DEVICE, "device list encode alloc");
   uint64_t* d_rows_at = (uint64_t*)meta;
-  uint64_t* d_levels = d_rows_at + np + 1;
+  uint64_t* d_head_at = d_rows_at + np + 1;
+  uint64_t* d_levels = d_head_at + np + 1;
   uint32_t* d_hlen = (uint32_t*)(d_levels + np);
-  std::vector<uint64_t> rows_at(np + 1), levels(np);
+  std::vector<uint64_t> rows_at(np + 1), head_at(np + 1), levels(np);
   hipLaunchKernelGGL(k_list_rows_at, dim3((uint32_t)((np + 256) / 256)), dim3(256), 0, st, d_offsets, n_rows, step, np,
                      d_rows_at);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess)
@@ -2389,6 +2378,8 @@ int encode_list_device(sb_ctx* ctx, int phys, const int64_t* d_offsets, const ui
   const uint64_t head_slot = (12 + 2 * 10 + (lmax + 7) / 8 + (2 * lmax + 7) / 8 + 15) & ~15ull;
   uint8_t* d_heads = (uint8_t*)ctx_scratch(ctx, np * head_slot, 6);
   if (!d_heads) return ctx_fail(ctx, SB_E_DEVICE, "device list encode alloc");
+  for (uint64_t q = 0; q <= np; q++) head_at[q] = q * head_slot;
+  hipLaunchKernelGGL(k_list_head_at, dim3((uint32_t)((np + 256) / 256)), dim3(256), 0, st, head_slot, np, d_head_at);
   sba::ListLv L{d_offsets, list_nullable ? d_list_validity : nullptr, item_nullable ? d_child_validity : nullptr,
                 n_rows, (uint32_t)step, list_nullable ? 1u : 0u, item_nullable ? 1u : 0u, d_heads, head_slot, d_hlen,
                 d_levels};
@@ -2402,7 +2393,7 @@ int encode_list_device(sb_ctx* ctx, int phys, const int64_t* d_offsets, const ui
     return ctx_fail(ctx, SB_E_DEVICE, "device list encode step 2");
   for (uint64_t q = 0; q < np; q++)
     if (levels[q] == ~0ull) return ctx_fail(ctx, SB_E_ARG, "decreasing list offsets");
-  const ListPart lp{d_rows_at, d_heads, head_slot, d_hlen, levels.data()};
+  const ListPart lp{d_rows_at, d_head_at, d_heads, d_hlen, rows_at.data(), head_at.data(), levels.data()};
   return encode_adaptive(ctx, phys, (const uint8_t*)d_child, item_nullable ? d_child_validity : nullptr, rows_at[np],
                          item_nullable, opts, P, d_out, out_cap, out_len, h_metas, np, &lp);
 }
@@ -2424,17 +2415,16 @@ static uint64_t binary_slot_bytes(uint64_t n, uint64_t vl, int ow, int nullable)
   return (pre + 256 + 2 * (n + 1) * ow + 32 + stream_bound(n, 4, 1) + 10 * n + 8192 + 3 * vl + 15) & ~15ull;
 }
 
-uint64_t binary_device_bound(uint64_t n_rows, uint64_t values_len, int ow, int nullable, uint64_t P) {
-  if (!P) return 0;
-  const uint64_t pages = (n_rows + P - 1) / P;
-  return pages * binary_slot_bytes(P, 0, ow, nullable) + 3 * values_len + 64;
+uint64_t binary_device_bound(const PagePlan& pl, uint64_t values_len, int ow, int nullable) {
+  if (!pl.np) return 0;
+  return pl.np * binary_slot_bytes(pl.step, 0, ow, nullable) + 3 * values_len + 64;
 }
 
 int encode_binary_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, uint64_t values_len,
                            const int64_t* d_offsets, const uint8_t* d_validity, uint64_t n_rows, int nullable,
                            const sb_write_options* opts, uint64_t P, uint8_t* d_out, uint64_t out_cap,
                            uint64_t* out_len, sb_page_meta* h_metas, uint64_t np, const ListPart* lp) {
-  const int ow = (phys == SB_T_BINARY || phys == SB_T_UTF8) ? 4 : (phys == SB_T_LARGE_BINARY || phys == SB_T_LARGE_UTF8) ? 8 : 0;
+  const int ow = (int)enc_type(phys).offset_width;
   if (!ow) return SB_E_NYI;
   const sba::Opts o{opts->default_codec, opts->has_ratio, opts->ratio, opts->forbidden_mask, opts->forced_codec};
   const bool stats = sba::needs_stats(o, o.forbidden);
@@ -2501,35 +2491,12 @@ int encode_binary_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, uint6
     sba::AdArgs a{d_values, d_validity, n_rows, (uint32_t)P, (uint32_t)b0, (uint32_t)(b1 - b0), nullable, o,
                   opts->seed, slots, 0, scratch, scr, work, gwork, gwb, sizes, status, offs, d_out, out_cap, (uint32_t)np,
                   d_offsets, values_len, ow, d_soff + batches[b].second};
-    if (lp) {
-      a.rows_at = lp->rows_at;
-      a.heads = lp->heads;
-      a.head_slot = lp->head_slot;
-      a.head_len = lp->head_len;
-      a.head_at = lp->head_at;
-    }
+    set_pages(a, lp);
     if (ow == 4) launch_bin<4>(a, lds, st);
     else launch_bin<8>(a, lds, st);
-    hipLaunchKernelGGL(sba::k_enc_offsets, dim3(1), dim3(sba::NT), 0, st, a);
-    hipLaunchKernelGGL(sba::k_enc_compact, dim3(a.n_batch), dim3(sba::NT), 0, st, a);
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess)
-      return ctx_fail(ctx, SB_E_DEVICE, "device encode launch (step 9)", (int)e);
+    if (int rc = place_batch(ctx, a, st, "device encode launch (step 9)")) return rc;
   }
-  std::vector<uint64_t> sz(2 * np + 1);
-  std::vector<uint32_t> stv(np);
-  if (hipMemcpyAsync(sz.data(), sizes, (2 * np + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(stv.data(), status, np * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    return ctx_fail(ctx, SB_E_DEVICE, "device encode step 10");
-  for (uint64_t p = 0; p < np; p++) {
-    if (stv[p] == sba::E_NYI) return SB_E_NYI;
-    if (stv[p] == sba::E_CAP) return SB_E_ARG;
-    if (stv[p]) return SB_E_OUT_OF_SPEC;
-  }
-  *out_len = sz[2 * np];
-  for (uint64_t p = 0; p < np; p++)
-    h_metas[p] = sb_page_meta{sz[p], lp ? lp->h_levels[p] : std::min<uint64_t>(P, n_rows - p * P)};
-  return SB_OK;
+  return finish_pages(ctx, st, sizes, status, np, P, n_rows, lp, out_len, h_metas, "device encode step 10");
 }
 
 // encode_chunk of one leaf of any nested field on the device (write/common.rs:
@@ -2538,24 +2505,13 @@ int encode_binary_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, uint6
 // level prefixes are built bottom-up in context scratch, k_nest_levels writes
 // each page's header, and the page's leaf slice goes through the page kernels
 // behind it.  Byte-identical to sb_encode_nested_column.
-static bool is_binary_type(int phys) { return phys >= SB_T_BINARY && phys <= SB_T_LARGE_UTF8; }
-static int enc_type_width(int phys) {
-  switch (phys) {
-    case SB_T_INT8: case SB_T_UINT8: return 1;
-    case SB_T_INT16: case SB_T_UINT16: return 2;
-    case SB_T_INT32: case SB_T_UINT32: case SB_T_FLOAT32: return 4;
-    case SB_T_INT64: case SB_T_UINT64: case SB_T_FLOAT64: return 8;
-  }
-  return 0;
-}
-
 int encode_nested_device(sb_ctx* ctx, const sb_nested_desc* desc, const sb_nest_dev* d_nests, const void* d_values,
                          const int64_t* d_leaf_offsets, uint64_t values_len, const uint8_t* d_leaf_validity,
                          uint64_t n_rows, const sb_write_options* opts, uint64_t step, uint8_t* d_out, uint64_t out_cap,
                          uint64_t* out_len, sb_page_meta* h_metas, uint64_t np) {
   hipStream_t st = (hipStream_t)sb_ctx_stream(ctx);
   const int depth = desc->depth, phys = desc->physical_type;
-  const bool binary = is_binary_type(phys);
+  const bool binary = enc_type(phys).offset_width != 0;
   // page metadata in one context slot: check results [2 x (depth + 1)] | lv_at |
   // rows_at | head_at [np + 1 each] u64 | head_len [np] u32
   const size_t meta_bytes = 16 * 8 + 3 * (np + 1) * 8 + np * 4;
@@ -2667,7 +2623,7 @@ int encode_nested_device(sb_ctx* ctx, const sb_nested_desc* desc, const sb_nest_
       hipMemcpyAsync(rows_at.data(), d_rows_at, (np + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
     return ctx_fail(ctx, SB_E_DEVICE, "device nested encode step 3");
-  uint64_t P = 1, head_max = 0;
+  uint64_t P = 1;
   head_at[0] = 0;
   for (uint64_t q = 0; q < np; q++) {
     if (rows_at[q + 1] < rows_at[q] || lv_at[q + 1] < lv_at[q]) return ctx_fail(ctx, SB_E_ARG, "decreasing offsets");
@@ -2677,7 +2633,6 @@ int encode_nested_device(sb_ctx* ctx, const sb_nested_desc* desc, const sb_nest_
     // 12 + per stream a ULEB128 run header + the packed levels
     const uint64_t hb = (12 + 2 * 10 + (levels[q] * a.bw_rep + 7) / 8 + (levels[q] * a.bw_def + 7) / 8 + 15) & ~15ull;
     head_at[q + 1] = head_at[q] + hb;
-    head_max = std::max(head_max, hb);
   }
   uint8_t* d_heads = (uint8_t*)ctx_scratch(ctx, head_at[np] + 16, 6);
   if (!d_heads) return ctx_fail(ctx, SB_E_DEVICE, "device nested encode alloc");
@@ -2692,10 +2647,7 @@ int encode_nested_device(sb_ctx* ctx, const sb_nested_desc* desc, const sb_nest_
     return ctx_fail(ctx, SB_E_DEVICE, "device nested encode launch (step 4)", (int)e);
   // 4. the leaf slices behind their headers (the page encoders synchronize the
   // stream before they return: head_at outlives its upload)
-  ListPart lp{d_rows_at, d_heads, head_max, d_hlen, levels.data()};
-  lp.head_at = d_head_at;
-  lp.h_rows_at = rows_at.data();
-  lp.h_head_at = head_at.data();
+  const ListPart lp{d_rows_at, d_head_at, d_heads, d_hlen, rows_at.data(), head_at.data(), levels.data()};
   const int has_valid = d_leaf_validity != nullptr;  // (feeds the statistics only: no prefix)
   if (binary)
     return encode_binary_adaptive(ctx, phys, (const uint8_t*)d_values, values_len, d_leaf_offsets, d_leaf_validity,
@@ -2707,10 +2659,9 @@ int encode_nested_device(sb_ctx* ctx, const sb_nested_desc* desc, const sb_nest_
 uint64_t nested_device_bound(const sb_nested_desc* desc, uint64_t n_rows, uint64_t n_level_bound, uint64_t n_leaf,
                              uint64_t values_len, uint64_t max_page_rows) {
   if (!desc) return 0;
-  const uint64_t step = max_page_rows ? std::min(max_page_rows, n_rows) : n_rows;
-  if (!step) return 0;
-  const uint64_t pages = (n_rows + step - 1) / step;
-  const int phys = desc->physical_type;
+  const uint64_t pages = PagePlan(n_rows, max_page_rows).np;
+  if (!pages) return 0;
+  const EncType t = enc_type(desc->physical_type);
   // the headers: 12 + two ULEB128 run headers a page, <= 3 + 4 bits a level, a
   // page's levels rounded up to bytes per stream
   const uint64_t heads = pages * (12 + 2 * 10 + 2) + n_level_bound;
@@ -2718,14 +2669,11 @@ uint64_t nested_device_bound(const sb_nested_desc* desc, uint64_t n_rows, uint64
   // sb_encode_list_device_bound), so the pages' slots sum to <= pages x slot(1) + slot(n_leaf)
   const uint64_t nl = std::max<uint64_t>(n_leaf, 1);
   uint64_t body;
-  if (is_binary_type(phys)) {
-    const int ow = (phys == SB_T_BINARY || phys == SB_T_UTF8) ? 4 : 8;
-    body = pages * binary_slot_bytes(1, 0, ow, 0) + binary_slot_bytes(nl, values_len, ow, 0);
-  } else {
-    const uint32_t w = phys == SB_T_BOOLEAN ? 1u : (uint32_t)enc_type_width(phys);
-    if (!w) return 0;
-    body = pages * adaptive_slot_bytes(1, w, 0) + adaptive_slot_bytes(nl, w, 0);
-  }
+  if (!t.supported()) return 0;
+  if (t.offset_width)
+    body = pages * binary_slot_bytes(1, 0, t.offset_width, 0) + binary_slot_bytes(nl, values_len, t.offset_width, 0);
+  else
+    body = pages * adaptive_slot_bytes(1, t.width, 0) + adaptive_slot_bytes(nl, t.width, 0);
   return heads + body + 64;
 }
 
@@ -2746,33 +2694,26 @@ extern "C" sb_status sb_encode_nested_column_device(sb_ctx* ctx, const sb_nested
   if (!ctx || !desc || !d_nests || !opts || !out_len || !n_pages) return SB_E_ARG;
   const int depth = desc->depth, phys = desc->physical_type;
   if (depth < 1 || depth > SB_MAX_NEST) return SB_E_NYI;
-  const bool binary = sb::is_binary_type(phys);
-  if (!binary && phys != SB_T_BOOLEAN && !sb::enc_type_width(phys)) return SB_E_NYI;
+  const bool binary = sb::enc_type(phys).offset_width != 0;
+  if (!sb::enc_type(phys).supported()) return SB_E_NYI;
   for (int d = 0; d < depth; d++) {
     if (!((desc->struct_mask >> d) & 1) && !d_nests[d].d_offsets) return SB_E_ARG;
     if (desc->list_nullable[d] && !d_nests[d].d_validity) return SB_E_ARG;
   }
   if ((desc->item_nullable && !d_leaf_validity) || (binary && !d_leaf_offsets) || (n_rows && (!d_out || !d_values)))
     return SB_E_ARG;
-  const uint64_t step = max_page_rows ? std::min(max_page_rows, n_rows) : n_rows;
-  const uint64_t np = step ? (n_rows + step - 1) / step : 0;
-  *n_pages = np;
-  if (np > metas_cap || (h_metas == nullptr && np)) return SB_E_ARG;
-  *out_len = 0;
-  if (!np) return SB_OK;
-  if (step > sba::kMaxRows) return SB_E_NYI;  // (as sb_encode_list_column_device)
-  if (hipSetDevice(sb_ctx_device(ctx)) != hipSuccess) return (sb_status)sb::ctx_fail(ctx, SB_E_DEVICE, "hipSetDevice");
+  const sb::PagePlan pl(n_rows, max_page_rows);  // (pages of at most kMaxRows rows, as sb_encode_list_column_device)
+  const sb_status rc = sb::begin_pages(ctx, pl, sba::kMaxRows, h_metas, metas_cap, n_pages, out_len);
+  if (rc != SB_OK || !pl.np) return rc;
   return (sb_status)sb::encode_nested_device(ctx, desc, d_nests, d_values, d_leaf_offsets, values_len, d_leaf_validity,
-                                             n_rows, opts, step, d_out, out_capacity, out_len, h_metas, np);
+                                             n_rows, opts, pl.step, d_out, out_capacity, out_len, h_metas, pl.np);
 }
 
 extern "C" uint64_t sb_encode_binary_device_bound(int32_t physical_type, uint64_t n_rows, uint64_t values_len,
                                                   int32_t nullable, uint64_t max_page_rows) {
-  const int ow = (physical_type == SB_T_BINARY || physical_type == SB_T_UTF8) ? 4
-                 : (physical_type == SB_T_LARGE_BINARY || physical_type == SB_T_LARGE_UTF8) ? 8 : 0;
-  const uint64_t P = max_page_rows ? std::min(max_page_rows, n_rows) : n_rows;
+  const int ow = (int)sb::enc_type(physical_type).offset_width;
   if (!ow) return 0;
-  return sb::binary_device_bound(n_rows, values_len, ow, nullable, P);
+  return sb::binary_device_bound(sb::PagePlan(n_rows, max_page_rows), values_len, ow, nullable);
 }
 
 extern "C" sb_status sb_encode_binary_column_device(sb_ctx* ctx, int32_t physical_type, const uint8_t* d_values,
@@ -2783,15 +2724,13 @@ extern "C" sb_status sb_encode_binary_column_device(sb_ctx* ctx, int32_t physica
                                                     sb_page_meta* h_metas, uint64_t metas_cap, uint64_t* n_pages) {
   if (!ctx || !opts || !out_len || !n_pages || (n_rows && (!d_offsets || !d_out)) || (nullable && !d_validity))
     return SB_E_ARG;
-  const uint64_t P = max_page_rows ? std::min(max_page_rows, n_rows) : n_rows;
-  const uint64_t np = n_rows ? (n_rows + P - 1) / P : 0;
-  *n_pages = np;
-  *out_len = 0;
-  if (np > metas_cap || (!h_metas && np)) return SB_E_ARG;
-  if (!np) return SB_OK;
-  if (hipSetDevice(sb_ctx_device(ctx)) != hipSuccess) return (sb_status)sb::ctx_fail(ctx, SB_E_DEVICE, "hipSetDevice");
+  const sb::PagePlan pl(n_rows, max_page_rows);
+  *out_len = 0;  // (this entry point clears it when h_metas has no room, too)
+  const sb_status rc = sb::begin_pages(ctx, pl, ~0ull, h_metas, metas_cap, n_pages, out_len);
+  if (rc != SB_OK || !pl.np) return rc;
   return (sb_status)sb::encode_binary_adaptive(ctx, physical_type, d_values, values_len, d_offsets, d_validity, n_rows,
-                                               nullable, opts, P, d_out, out_capacity, out_len, h_metas, np, nullptr);
+                                               nullable, opts, pl.step, d_out, out_capacity, out_len, h_metas, pl.np,
+                                               nullptr);
 }
 
 #ifdef SB_ENC_PHASES

@@ -21,8 +21,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "../../include/strawboat_gpu.h"
-#include "sb_internal.h"
+#include "sb_encode_dev.h"
 
 namespace sbe {
 
@@ -51,16 +50,11 @@ __device__ __forceinline__ uint32_t page_n(const EncArgs& a, uint32_t p) {
   const uint64_t r0 = (uint64_t)p * a.page_rows;
   return (uint32_t)min<uint64_t>(a.page_rows, a.n_rows - r0);
 }
-__device__ __forceinline__ uint32_t uleb_len(uint64_t h) {
-  uint32_t l = 1;
-  while (h >= 0x80) { h >>= 7; l++; }
-  return l;
-}
 // validity prefix bytes: u32 def_len + ULEB128((nbytes << 1) | 1) + nbytes
 __device__ __forceinline__ uint32_t prefix_len(const EncArgs& a, uint32_t n) {
   if (!a.nullable) return 0;
   const uint32_t nb = (n + 7) / 8;
-  return 4 + uleb_len(((uint64_t)nb << 1) | 1) + nb;
+  return 4 + sb::uleb_len(((uint64_t)nb << 1) | 1) + nb;
 }
 __device__ __forceinline__ uint32_t wave_or(uint32_t v) {
   for (int d = 32; d; d >>= 1) v |= __shfl_xor(v, d, 64);
@@ -166,12 +160,12 @@ __global__ __launch_bounds__(NT) void k_enc_write(EncArgs a) {
     uint32_t q = 0;
     if (a.nullable) {  // write_validity
       const uint32_t nb = (n + 7) / 8;
-      uint64_t h = ((uint64_t)nb << 1) | 1;
-      const uint32_t hl = uleb_len(h);
+      const uint64_t h = ((uint64_t)nb << 1) | 1;
+      const uint32_t hl = sb::uleb_len(h);
       if (tid == 0) {
         const uint32_t dl = hl + nb;
         for (int j = 0; j < 4; j++) pg[j] = (uint8_t)(dl >> (8 * j));
-        for (uint32_t j = 0; j < hl; j++, h >>= 7) pg[4 + j] = (uint8_t)((h & 0x7F) | (j + 1 < hl ? 0x80 : 0));
+        sb::put_uleb(pg + 4, h);
       }
       for (uint32_t j = tid; j < nb; j += NT) {
         const uint64_t bit0 = r0 + 8ull * j;
@@ -239,38 +233,16 @@ __global__ __launch_bounds__(NT) void k_enc_write(EncArgs a) {
 
 }  // namespace sbe
 
-static uint32_t type_width(int32_t t) {
-  switch (t) {
-    case SB_T_INT8: case SB_T_UINT8: return 1;
-    case SB_T_INT16: case SB_T_UINT16: return 2;
-    case SB_T_INT32: case SB_T_UINT32: case SB_T_FLOAT32: return 4;
-    case SB_T_INT64: case SB_T_UINT64: case SB_T_FLOAT64: return 8;
-  }
-  return 0;
-}
-
-namespace sb {
-struct ListPart;
-uint64_t adaptive_slot_bytes(uint64_t P, uint32_t w, int nullable);
-int encode_adaptive(sb_ctx* ctx, int phys, const uint8_t* d_values, const uint8_t* d_validity, uint64_t n_rows,
-                    int nullable, const sb_write_options* opts, uint64_t P, uint8_t* d_out, uint64_t out_cap,
-                    uint64_t* out_len, sb_page_meta* h_metas, uint64_t np, const ListPart* lp);
-int encode_list_device(sb_ctx* ctx, int phys, const int64_t* d_offsets, const uint8_t* d_list_validity,
-                       int list_nullable, const void* d_child, const uint8_t* d_child_validity, int item_nullable,
-                       uint64_t n_rows, const sb_write_options* opts, uint64_t step, uint8_t* d_out, uint64_t out_cap,
-                       uint64_t* out_len, sb_page_meta* h_metas, uint64_t np);
-}  // namespace sb
-
 extern "C" uint64_t sb_encode_device_bound(int32_t physical_type, uint64_t n_rows, int32_t nullable,
                                            uint64_t max_page_rows) {
-  const uint64_t w = physical_type == SB_T_BOOLEAN ? 1 : type_width(physical_type);
-  const uint64_t P = max_page_rows ? std::min(max_page_rows, n_rows) : n_rows;
+  const uint64_t w = sb::enc_type(physical_type).width;
+  const sb::PagePlan pl(n_rows, max_page_rows);
+  const uint64_t P = pl.step;
   if (!w || !P) return 0;
-  const uint64_t pages = (n_rows + P - 1) / P;
   // per page: prefix (4 + <= 10 + P/8) + header 9 + max(raw, bitpacked at b = 32)
   const uint64_t fast = (nullable ? 14 + (P + 7) / 8 : 0) + 9 + std::max(P * w, P / 128 * 513) + 16;
   // the adaptive cascade's worst case (forced RLE, Dict / Freq cascades)
-  return pages * std::max(fast, sb::adaptive_slot_bytes(P, (uint32_t)w, nullable));
+  return pl.np * std::max(fast, sb::adaptive_slot_bytes(P, (uint32_t)w, nullable));
 }
 
 extern "C" sb_status sb_encode_column_device(sb_ctx* ctx, int32_t physical_type, const void* d_values,
@@ -280,16 +252,12 @@ extern "C" sb_status sb_encode_column_device(sb_ctx* ctx, int32_t physical_type,
                                              uint64_t metas_cap, uint64_t* n_pages) {
   if (!ctx || !opts || !out_len || !n_pages) return SB_E_ARG;
   const bool is_bool = physical_type == SB_T_BOOLEAN;  // d_values = the column's LSB bitmap
-  const uint32_t w = is_bool ? 1 : type_width(physical_type);
-  // page_size = max_page_size.unwrap_or(len).min(len) (write/common.rs:54-58)
-  const uint64_t P = max_page_rows ? std::min(max_page_rows, n_rows) : n_rows;
+  const uint32_t w = sb::enc_type(physical_type).width;
   if (!w || (nullable && !d_validity) || (n_rows && (!d_values || !d_out))) return SB_E_ARG;
-  const uint64_t np = n_rows ? (n_rows + P - 1) / P : 0;
-  *n_pages = np;
-  if (np > metas_cap || (h_metas == nullptr && np)) return SB_E_ARG;
-  *out_len = 0;
-  if (!np) return SB_OK;
-  if (hipSetDevice(sb_ctx_device(ctx)) != hipSuccess) return SB_E_DEVICE;
+  const sb::PagePlan pl(n_rows, max_page_rows);
+  const uint64_t P = pl.step, np = pl.np;
+  const sb_status rc = sb::begin_pages(ctx, pl, ~0ull, h_metas, metas_cap, n_pages, out_len);
+  if (rc != SB_OK || !np) return rc;
   // Options whose codec choice needs no trial compression (ratio None, default
   // None, forced codec none or Bitpacking: choose_compressor,
   // integer/mod.rs:231-240) take the sizing + assembly fast path; every other
@@ -337,10 +305,9 @@ extern "C" sb_status sb_encode_column_device(sb_ctx* ctx, int32_t physical_type,
 // (include/strawboat_gpu.h; byte-identical to sb_encode_list_column).
 extern "C" uint64_t sb_encode_list_device_bound(int32_t physical_type, uint64_t n_rows, uint64_t n_child,
                                                 int32_t item_nullable, uint64_t max_page_rows) {
-  const uint64_t w = type_width(physical_type);
-  const uint64_t P = max_page_rows ? std::min(max_page_rows, n_rows) : n_rows;
-  if (!w || !P) return 0;
-  const uint64_t pages = (n_rows + P - 1) / P;
+  const uint64_t w = sb::enc_type(physical_type).value_width();
+  const uint64_t pages = sb::PagePlan(n_rows, max_page_rows).np;
+  if (!w || !pages) return 0;
   // the level headers (<= 12 + 20 + (rows + values) * 3 / 8 + 1 a page) and
   // the child values' pages: adaptive_slot_bytes is affine in the rows, so
   // the pages' slots sum to <= pages x slot(1) + slot(n_child)
@@ -356,18 +323,14 @@ extern "C" sb_status sb_encode_list_column_device(sb_ctx* ctx, int32_t physical_
                                                   uint64_t out_capacity, uint64_t* out_len, sb_page_meta* h_metas,
                                                   uint64_t metas_cap, uint64_t* n_pages) {
   if (!ctx || !opts || !out_len || !n_pages || !d_offsets) return SB_E_ARG;
-  if (!type_width(physical_type)) return SB_E_NYI;
+  if (!sb::enc_type(physical_type).value_width()) return SB_E_NYI;
   if ((list_nullable && !d_list_validity) || (item_nullable && !d_child_validity) || (n_rows && !d_out))
     return SB_E_ARG;
-  const uint64_t step = max_page_rows ? std::min(max_page_rows, n_rows) : n_rows;
-  const uint64_t np = step ? (n_rows + step - 1) / step : 0;
-  *n_pages = np;
-  if (np > metas_cap || (h_metas == nullptr && np)) return SB_E_ARG;
-  *out_len = 0;
-  if (!np) return SB_OK;
-  if (step > sbe::kMaxPageRows) return SB_E_NYI;  // (the level prefix of a page lives in LDS)
-  if (hipSetDevice(sb_ctx_device(ctx)) != hipSuccess) return SB_E_DEVICE;
+  const sb::PagePlan pl(n_rows, max_page_rows);
+  // (pages of at most kMaxPageRows rows: the level prefix of a page lives in LDS)
+  const sb_status rc = sb::begin_pages(ctx, pl, sbe::kMaxPageRows, h_metas, metas_cap, n_pages, out_len);
+  if (rc != SB_OK || !pl.np) return rc;
   return (sb_status)sb::encode_list_device(ctx, physical_type, d_offsets, d_list_validity, list_nullable, d_child,
-                                           d_child_validity, item_nullable, n_rows, opts, step, d_out, out_capacity,
-                                           out_len, h_metas, np);
+                                           d_child_validity, item_nullable, n_rows, opts, pl.step, d_out, out_capacity,
+                                           out_len, h_metas, pl.np);
 }

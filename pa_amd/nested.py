@@ -101,7 +101,7 @@ def encode_list_column_device(offsets, child, list_validity=None, child_validity
     import torch
 
     from .read import resolve_context
-    from .write import WriteOptions
+    from .write import WriteOptions, pack_bits, page_rows, run_device_encode, torch_physical_type
 
     L = _lib()
     options = options or WriteOptions()
@@ -109,43 +109,24 @@ def encode_list_column_device(offsets, child, list_validity=None, child_validity
     offs = offsets.to(torch.int64).contiguous()
     child = child.contiguous()
     n = offs.numel() - 1
-    tdt = {torch.int8: np.int8, torch.int16: np.int16, torch.int32: np.int32, torch.int64: np.int64,
-           torch.uint8: np.uint8, torch.uint16: np.uint16, torch.uint32: np.uint32, torch.uint64: np.uint64,
-           torch.float32: np.float32, torch.float64: np.float64}[child.dtype]
-    phys = physical_type(np.dtype(tdt))
-
-    def pack(bits, m):  # bool device tensor -> LSB-first bitmap bytes (at least one byte)
-        bits = bits.to(device=child.device, dtype=torch.bool).reshape(-1)
-        pad = (-m) % 8
-        if pad:
-            bits = torch.cat([bits, torch.zeros(pad, dtype=torch.bool, device=bits.device)])
-        if not m:
-            return torch.zeros(1, dtype=torch.uint8, device=child.device)
-        w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=child.device)
-        return (bits.view(-1, 8).to(torch.uint8) * w).sum(1, dtype=torch.uint8)
-
+    dev = child.device
+    phys = torch_physical_type(child.dtype)
     nc = child.numel()
-    lvb = pack(list_validity if list_validity is not None else torch.ones(n, dtype=torch.bool), n) \
+    lvb = pack_bits(list_validity if list_validity is not None else torch.ones(n, dtype=torch.bool), n, dev) \
         if list_nullable else None
-    cvb = pack(child_validity if child_validity is not None else torch.ones(nc, dtype=torch.bool), nc) \
+    cvb = pack_bits(child_validity if child_validity is not None else torch.ones(nc, dtype=torch.bool), nc, dev) \
         if item_nullable else None
     if nc == 0:
-        child = torch.zeros(1, dtype=child.dtype, device=child.device)
-    P = min(options.max_page_size or n, n)
+        child = torch.zeros(1, dtype=child.dtype, device=dev)
+    P, npages = page_rows(options, n)
     n_child = int(offs[-1].item() - offs[0].item()) if n else 0
-    cap = L.sb_encode_list_device_bound(phys, n, n_child, int(item_nullable), P)
-    out = torch.empty(max(cap, 16), dtype=torch.uint8, device=child.device)
-    npages = (n + P - 1) // P if n else 0
-    metas = (N.PageMetaC * max(npages, 1))()
-    olen, npg = ctypes.c_uint64(), ctypes.c_uint64()
     opts = options.c()
     vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    st = L.sb_encode_list_column_device(ctx._h, phys, vp(offs), vp(lvb), int(list_nullable), vp(child), vp(cvb),
-                                        int(item_nullable), n, ctypes.byref(opts), P, vp(out), out.numel(),
-                                        ctypes.byref(olen), metas, max(npages, 1), ctypes.byref(npg))
-    if st:
-        raise N.StrawboatError(st, "encode_list_column_device: " + ctx.error())
-    return out[: olen.value], [PageMeta(metas[i].length, metas[i].num_values) for i in range(npg.value)]
+    return run_device_encode(
+        "encode_list_column_device", ctx, dev, L.sb_encode_list_device_bound(phys, n, n_child, int(item_nullable), P),
+        npages, lambda *out: L.sb_encode_list_column_device(
+            ctx._h, phys, vp(offs), vp(lvb), int(list_nullable), vp(child), vp(cvb), int(item_nullable), n,
+            ctypes.byref(opts), P, *out))
 
 
 class ListColumnDecoder:
@@ -791,7 +772,7 @@ def encode_field_device(fld: Field, arr: DeviceArray, options=None, ctx=None):
     the device's own frames)."""
     import torch
 
-    from .write import WriteOptions
+    from .write import WriteOptions, pack_bits, page_rows, run_device_encode
 
     if fld.kind == "leaf":
         raise N.StrawboatError(N.E_ARG, "a primitive field is not nested: use encode_column_device")
@@ -829,14 +810,8 @@ def encode_field_device(fld: Field, arr: DeviceArray, options=None, ctx=None):
             return cache[("ones", n)]
         key = ("b", id(t))
         if key not in cache:
-            if t.dtype == torch.bool:  # packed on the device, LSB first
-                bits = t.to(dev).reshape(-1)[:n]
-                pad = (-n) % 8
-                if pad:
-                    bits = torch.cat([bits, torch.zeros(pad, dtype=torch.bool, device=dev)])
-                w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=dev)
-                cache[key] = (bits.view(-1, 8).to(torch.uint8) * w).sum(1, dtype=torch.uint8) if n else \
-                    torch.zeros(1, dtype=torch.uint8, device=dev)
+            if t.dtype == torch.bool:
+                cache[key] = pack_bits(t, n, dev)
             else:
                 cache[key] = t.to(dev).contiguous() if t.numel() else torch.zeros(1, dtype=torch.uint8, device=dev)
         return cache[key]
@@ -849,8 +824,7 @@ def encode_field_device(fld: Field, arr: DeviceArray, options=None, ctx=None):
 
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     n_rows = arr.length
-    P = min(options.max_page_size or n_rows, n_rows)
-    npages = (n_rows + P - 1) // P if n_rows else 0
+    P, npages = page_rows(options, n_rows)
     out_cols = []
     for path in paths:
         nulls, mask, leaf_null, large = init_chain(path)
@@ -885,15 +859,11 @@ def encode_field_device(fld: Field, arr: DeviceArray, options=None, ctx=None):
         desc = NestedDescC(phys, depth, ln, int(leaf_null), 8 if large else 4, mask)
         n_level_bound = sum(a.length for a in arrs)
         cap = nested_device_bound(desc, n_rows, n_level_bound, la.length, vlen, P)
-        out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
-        metas = (N.PageMetaC * max(npages, 1))()
-        olen, npg = ctypes.c_uint64(), ctypes.c_uint64()
-        st = L.sb_encode_nested_column_device(ctx._h, ctypes.byref(desc), nests, ptr(vals), ptr(lo), vlen, ptr(lvb),
-                                              n_rows, ctypes.byref(opts), P, ptr(out), out.numel(), ctypes.byref(olen),
-                                              metas, max(npages, 1), ctypes.byref(npg))
-        if st:
-            raise N.StrawboatError(st, "encode_nested_column_device: " + ctx.error())
-        out_cols.append((out[: olen.value], [PageMeta(metas[i].length, metas[i].num_values) for i in range(npg.value)]))
+        out_cols.append(run_device_encode(
+            "encode_nested_column_device", ctx, dev, cap, npages,
+            lambda *out: L.sb_encode_nested_column_device(
+                ctx._h, ctypes.byref(desc), nests, ptr(vals), ptr(lo), vlen, ptr(lvb), n_rows, ctypes.byref(opts), P,
+                *out)))
     return out_cols
 
 

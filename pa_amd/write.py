@@ -47,6 +47,51 @@ class WriteOptions:
         return N.WriteOptionsC(self.default_compression, r is not None, float(r or 0.0), m, self.forced_codec, self.seed)
 
 
+def pack_bits(bits, n: int, device):
+    """A bool tensor's first n bits -> LSB-first bitmap bytes on the device (at least one byte)."""
+    import torch
+
+    if not n:
+        return torch.zeros(1, dtype=torch.uint8, device=device)
+    bits = bits.to(device=device, dtype=torch.bool).reshape(-1)[:n]
+    pad = (-n) % 8
+    if pad:
+        bits = torch.cat([bits, torch.zeros(pad, dtype=torch.bool, device=device)])
+    w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=device)
+    return (bits.view(-1, 8).to(torch.uint8) * w).sum(1, dtype=torch.uint8)
+
+
+def torch_physical_type(dtype) -> int:
+    """The physical type of a fixed-width torch dtype (bool is not one: KeyError)."""
+    import torch
+
+    return physical_type(np.dtype({
+        torch.int8: np.int8, torch.int16: np.int16, torch.int32: np.int32, torch.int64: np.int64,
+        torch.uint8: np.uint8, torch.uint16: np.uint16, torch.uint32: np.uint32, torch.uint64: np.uint64,
+        torch.float32: np.float32, torch.float64: np.float64}[dtype]))
+
+
+def page_rows(options: WriteOptions, n: int) -> Tuple[int, int]:
+    """(rows a page, pages): page_size = max_page_size.unwrap_or(len).min(len) (write/common.rs:54-58)."""
+    P = min(options.max_page_size or n, n)
+    return P, ((n + P - 1) // P if n else 0)
+
+
+def run_device_encode(name: str, ctx, device, cap: int, npages: int, call):
+    """The device entry points' output protocol: a chunk buffer of the bound's
+    size and room for npages metas, call(d_out, out_capacity, out_len, h_metas,
+    metas_cap, n_pages) -> status; returns (chunk[:out_len], [PageMeta])."""
+    import torch
+
+    out = torch.empty(max(cap, 16), dtype=torch.uint8, device=device)
+    metas = (N.PageMetaC * max(npages, 1))()
+    olen, npg = ctypes.c_uint64(), ctypes.c_uint64()
+    st = call(ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.byref(olen), metas, max(npages, 1), ctypes.byref(npg))
+    if st:
+        raise N.StrawboatError(st, name + ": " + ctx.error())
+    return out[: olen.value], [PageMeta(metas[i].length, metas[i].num_values) for i in range(npg.value)]
+
+
 def _take(ptr, n) -> bytes:
     b = ctypes.string_at(ptr, n) if n else b""
     N.lib().sb_free(ptr)
@@ -101,44 +146,23 @@ def encode_column_device(values, validity=None, nullable: bool = False, options:
     ctx = resolve_context(ctx, values)
     values = values.contiguous()
     n = values.numel()
-
-    def pack(bits):  # bool device tensor -> LSB-first bitmap bytes (at least one byte)
-        pad = (-n) % 8
-        if pad:
-            bits = torch.cat([bits, torch.zeros(pad, dtype=torch.bool, device=bits.device)])
-        w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=bits.device)
-        if not n:
-            return torch.zeros(1, dtype=torch.uint8, device=bits.device)
-        return (bits.view(-1, 8).to(torch.uint8) * w).sum(1, dtype=torch.uint8)
-
+    dev = values.device
     if values.dtype == torch.bool:  # compress_boolean takes the column's bitmap; pages slice it
         phys = N.BOOLEAN
-        values = pack(values.reshape(-1))
+        values = pack_bits(values, n, dev)
     else:
-        tdt = {torch.int8: np.int8, torch.int16: np.int16, torch.int32: np.int32, torch.int64: np.int64,
-               torch.uint8: np.uint8, torch.uint16: np.uint16, torch.uint32: np.uint32, torch.uint64: np.uint64,
-               torch.float32: np.float32, torch.float64: np.float64}[values.dtype]
-        phys = physical_type(np.dtype(tdt))
+        phys = torch_physical_type(values.dtype)
     vb = None
     if nullable:
         # a missing bitmap is all-valid (write_def_levels' (is_optional, None) case), as in encode_column
-        vb = pack(validity.to(device=values.device, dtype=torch.bool).reshape(-1) if validity is not None
-                  else torch.ones(n, dtype=torch.bool, device=values.device))
-    # page_size = max_page_size.unwrap_or(len).min(len) (write/common.rs:54-58)
-    P = min(options.max_page_size or n, n)
-    cap = N.lib().sb_encode_device_bound(phys, n, int(nullable), P)
-    out = torch.empty(max(cap, 16), dtype=torch.uint8, device=values.device)
-    npages = (n + P - 1) // P if n else 0
-    metas = (N.PageMetaC * max(npages, 1))()
-    olen, npg = ctypes.c_uint64(), ctypes.c_uint64()
+        vb = pack_bits(validity if validity is not None else torch.ones(n, dtype=torch.bool, device=dev), n, dev)
+    P, npages = page_rows(options, n)
     opts = options.c()
-    st = N.lib().sb_encode_column_device(
-        ctx._h, phys, ctypes.c_void_p(values.data_ptr()), None if vb is None else ctypes.c_void_p(vb.data_ptr()), n,
-        int(nullable), ctypes.byref(opts), P, ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.byref(olen),
-        metas, max(npages, 1), ctypes.byref(npg))
-    if st:
-        raise N.StrawboatError(st, "encode_column_device: " + ctx.error())
-    return out[: olen.value], [PageMeta(metas[i].length, metas[i].num_values) for i in range(npg.value)]
+    return run_device_encode(
+        "encode_column_device", ctx, dev, N.lib().sb_encode_device_bound(phys, n, int(nullable), P), npages,
+        lambda *out: N.lib().sb_encode_column_device(
+            ctx._h, phys, ctypes.c_void_p(values.data_ptr()), None if vb is None else ctypes.c_void_p(vb.data_ptr()),
+            n, int(nullable), ctypes.byref(opts), P, *out))
 
 
 @dataclass
