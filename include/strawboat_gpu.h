@@ -342,7 +342,10 @@ sb_status sb_encode_binary_column(int32_t physical_type, const uint8_t* h_values
  * h_offsets = n_rows + 1 absolute int64 positions into h_child (the child
  * column's values, sizeof(physical_type) each); h_list_validity is over the
  * rows, h_child_validity over the child values (either may be NULL).
- * PageMeta.num_values of each page is its level count (num_values(nested)). */
+ * PageMeta.num_values of each page is its level count (num_values(nested)).
+ * A null list slot must be empty (h_offsets[i + 1] == h_offsets[i]): it emits
+ * one level and no leaf slot, while the leaf slice is taken through the
+ * offsets.  SB_E_ARG otherwise, before any page is written. */
 sb_status sb_encode_list_column(int32_t physical_type, const int64_t* h_offsets, const uint8_t* h_list_validity,
                                 int32_t list_nullable, const void* h_child, const uint8_t* h_child_validity,
                                 int32_t item_nullable, uint64_t n_rows, const sb_write_options* opts,
@@ -370,7 +373,16 @@ typedef struct {
  * header and stats use).  h_leaf_validity over the slots (NULL = none).  A
  * Struct / Map field is written by one call per leaf, in to_leaves order.
  * PageMeta.num_values = the page's level count.  Page p samples with
- * sb_page_seed(opts->seed, p).  SB_E_ARG for decreasing offsets. */
+ * sb_page_seed(opts->seed, p).  SB_E_ARG for decreasing or negative offsets.
+ * Dead slots: a slot is dead if it is null itself, or if the same index is
+ * null in any struct nest of the run of struct nests directly above it.  A
+ * dead slot emits one level and no leaf slot, while the leaf slice is taken
+ * through the offsets, so a dead list / map slot must be empty (offsets[i + 1]
+ * == offsets[i]): SB_E_ARG otherwise, before any page is written.  Everything
+ * else a legal Arrow array may hold is taken and written as its logical
+ * value: valid children and valid empty lists under a null struct slot,
+ * offsets that start above 0 (nests and Binary leaves), children longer than
+ * the offsets reach, a nullable nest with a NULL bitmap (all valid). */
 sb_status sb_encode_nested_column(const sb_nested_desc* desc, const sb_nest_in* h_nests, const void* h_values,
                                   const int64_t* h_leaf_offsets, uint64_t values_len, const uint8_t* h_leaf_validity,
                                   uint64_t n_rows, const sb_write_options* opts, uint64_t max_page_rows,
@@ -436,8 +448,10 @@ sb_status sb_encode_binary_column_device(sb_ctx* ctx, int32_t physical_type, con
  * positions into d_child; d_list_validity over the rows, d_child_validity over
  * the child values (device LSB bitmaps).  d_out holds at least
  * sb_encode_list_device_bound(.., n_child = d_offsets[n_rows] - d_offsets[0],
- * ..) bytes; PageMeta.num_values = the page's level count.  Synchronizes the
- * context's stream. */
+ * ..) bytes; PageMeta.num_values = the page's level count.  A null list slot
+ * must be empty, as for sb_encode_list_column: SB_E_ARG otherwise (the level
+ * kernel finds it; nothing is written to d_out).  Synchronizes the context's
+ * stream. */
 uint64_t sb_encode_list_device_bound(int32_t physical_type, uint64_t n_rows, uint64_t n_child, int32_t item_nullable,
                                      uint64_t max_page_rows);
 sb_status sb_encode_list_column_device(sb_ctx* ctx, int32_t physical_type, const int64_t* d_offsets,
@@ -467,9 +481,12 @@ typedef struct {
  * Zstd default codec writes the device's own frames.  PageMeta.num_values =
  * the page's level count; page p samples with sb_page_seed(opts->seed, p).
  * SB_E_ARG: NULL ctx / opts / output pointers, a missing bitmap, offsets that
- * decrease (or are negative) at any nest or at the leaf, a d_out or metas_cap
- * too small.  d_out holds at least sb_encode_nested_device_bound(..) bytes:
- * n_level_bound = the entries of every nest + the leaf slots (no page holds
+ * decrease (or are negative) at any nest or at the leaf, a dead list / map
+ * slot that is not empty (sb_encode_nested_column's rule: null itself, or
+ * null in a struct of the run of struct nests directly above; the offsets
+ * check of each nest reads those bitmaps, before any page is written), a
+ * d_out or metas_cap too small.  d_out holds at least
+ * sb_encode_nested_device_bound(..) bytes: n_level_bound = the entries of every nest + the leaf slots (no page holds
  * more levels), n_leaf = the leaf slots; host only.  Synchronizes the
  * context's stream. */
 uint64_t sb_encode_nested_device_bound(const sb_nested_desc* desc, uint64_t n_rows, uint64_t n_level_bound,

@@ -22,7 +22,20 @@ order, and read back leaf by leaf -- the reference's shape:
 The levels are restated as the Dremel encoding arrow2's RepLevelsIter /
 DefLevelsIter produce for arrays whose children are null under a null
 parent (the arrays arrow2 / pyarrow build from Python None); they are pinned
-against pyarrow's parquet writer (tests/test_pyarrow_nested.py)."""
+against pyarrow's parquet writer (tests/test_pyarrow_nested.py).
+
+Precondition of the writer (write_field / levels): a dead list / map slot is
+empty.  A slot is dead if it is null itself, or if the same index is null in
+any struct of the run of struct nests directly above it; it emits one level
+and no leaf slot, while the leaf slice [j0, j1) is taken through the offsets,
+so a dead slot with children would put values in the page that no level
+pairs (read_nested_page then fails, out of spec).  The product writers
+refuse such an array (SB_E_ARG); this writer does not look.  Nothing else
+of the normal form is needed: children of a null struct slot may be valid
+(the walk stops at the null struct and never reads them), offsets may start
+above 0, children may be longer than the offsets reach, and a nullable nest
+with validity None is all valid.  read_field returns the logical value:
+children of a null struct slot read back null, offsets from 0."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field

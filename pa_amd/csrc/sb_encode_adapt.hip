@@ -1872,12 +1872,14 @@ __global__ __launch_bounds__(NT) void k_enc_list_levels(ListLv a) {
   __syncthreads();
   const uint32_t ch = (m + NT - 1) / NT, b0 = min(m, tid * ch), b1 = min(m, b0 + ch);
   uint32_t sum = 0;
-  bool bad = false;
+  bool bad = false, dead = false;  // dead: a null slot that is not empty (its children would reach the leaf slice)
   for (uint32_t r = b0; r < b1; r++) {
     sum += row_levels(r);
-    bad |= a.offsets[r0 + r + 1] < a.offsets[r0 + r];
+    const int64_t len = a.offsets[r0 + r + 1] - a.offsets[r0 + r];
+    bad |= len < 0;
+    dead |= len > 0 && a.nl && a.lvalid && !bit_at(a.lvalid, r0 + r);
   }
-  if (bad) atomicOr(&s_bad, 1u);
+  if (bad | dead) atomicOr(&s_bad, bad ? 1u : 2u);
   uint32_t x = sum;
   for (uint32_t d = 1; d < 64; d <<= 1) {
     const uint32_t y = __shfl_up(x, d, 64);
@@ -1899,7 +1901,7 @@ __global__ __launch_bounds__(NT) void k_enc_list_levels(ListLv a) {
   if (s_bad) {  // every thread sees the flag after the barrier: the page is refused whole
     if (tid == 0) {
       a.head_len[p] = 0;
-      a.levels[p] = ~0ull;
+      a.levels[p] = (s_bad & 1) ? ~0ull : ~1ull;
     }
     return;
   }
@@ -1982,10 +1984,29 @@ struct NestLv {
 
 __device__ __forceinline__ uint64_t pre_at(const uint64_t* C, uint64_t i) { return C ? C[i] : i; }
 
-// offsets [0, count]: non-negative and non-decreasing, else *bad; res[1] = o[count]
-__global__ void k_nest_check(const int64_t* o, uint64_t count, uint64_t* res) {
+// The bitmaps under which slot i of a list nest is dead: the nest's own and
+// those of the nullable structs in the run of struct nests directly above it
+// (a struct passes its slot index through).  A dead slot emits one level and
+// no leaf slot, so it must be empty: the leaf slice is taken through the offsets.
+struct NestDead {
+  const uint8_t* bm[4];
+  int n;
+};
+
+// offsets [0, count]: non-negative and non-decreasing, else res[0] |= 1; a
+// dead slot that is not empty: res[0] |= 2; res[1] = o[count]
+__global__ void k_nest_check(const int64_t* o, uint64_t count, NestDead dead, uint64_t* res) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count && (o[i] < 0 || o[i + 1] < o[i])) res[0] = 1;
+  if (i < count) {
+    const int64_t b = o[i], e = o[i + 1];
+    if (b < 0 || e < b) {
+      atomicOr((unsigned long long*)res, 1ull);
+    } else if (e > b) {
+      bool live = true;
+      for (int k = 0; k < dead.n; k++) live &= bit_at(dead.bm[k], i);
+      if (!live) atomicOr((unsigned long long*)res, 2ull);
+    }
+  }
   if (i == count) res[1] = (uint64_t)o[count];
 }
 
@@ -2391,8 +2412,10 @@ int encode_list_device(sb_ctx* ctx, int phys, const int64_t* d_offsets, const ui
   if (hipMemcpyAsync(levels.data(), d_levels, np * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
     return ctx_fail(ctx, SB_E_DEVICE, "device list encode step 2");
-  for (uint64_t q = 0; q < np; q++)
+  for (uint64_t q = 0; q < np; q++) {
     if (levels[q] == ~0ull) return ctx_fail(ctx, SB_E_ARG, "decreasing list offsets");
+    if (levels[q] == ~1ull) return ctx_fail(ctx, SB_E_ARG, "a null list slot is not empty");
+  }
   const ListPart lp{d_rows_at, d_head_at, d_heads, d_hlen, rows_at.data(), head_at.data(), levels.data()};
   return encode_adaptive(ctx, phys, (const uint8_t*)d_child, item_nullable ? d_child_validity : nullptr, rows_at[np],
                          item_nullable, opts, P, d_out, out_cap, out_len, h_metas, np, &lp);
@@ -2522,18 +2545,19 @@ int encode_nested_device(sb_ctx* ctx, const sb_nested_desc* desc, const sb_nest_
   uint64_t* d_rows_at = d_lv_at + np + 1;
   uint64_t* d_head_at = d_rows_at + np + 1;
   uint32_t* d_hlen = (uint32_t*)(d_head_at + np + 1);
-  // 1. top-down: offsets never decrease; entries per nest
+  // 1. top-down: offsets never decrease, dead slots are empty; entries per nest
   uint64_t count[SB_MAX_NEST + 1];
   count[0] = n_rows;
   uint64_t res[2];
-  auto check = [&](const int64_t* o, uint64_t cnt, uint64_t* last) -> int {
+  auto check = [&](const int64_t* o, uint64_t cnt, const sba::NestDead& dead, uint64_t* last) -> int {
     if (hipMemsetAsync(d_res, 0, 16, st) != hipSuccess) return ctx_fail(ctx, SB_E_DEVICE, "device nested encode step 1");
-    hipLaunchKernelGGL(sba::k_nest_check, dim3((uint32_t)(cnt / 256 + 1)), dim3(256), 0, st, o, cnt, d_res);
+    hipLaunchKernelGGL(sba::k_nest_check, dim3((uint32_t)(cnt / 256 + 1)), dim3(256), 0, st, o, cnt, dead, d_res);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess)
       return ctx_fail(ctx, SB_E_DEVICE, "device nested encode launch (step 1)", (int)e);
     if (hipMemcpyAsync(res, d_res, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
       return ctx_fail(ctx, SB_E_DEVICE, "device nested encode step 1");
-    if (res[0] || (int64_t)res[1] < 0) return ctx_fail(ctx, SB_E_ARG, "decreasing offsets");
+    if ((res[0] & 1) || (int64_t)res[1] < 0) return ctx_fail(ctx, SB_E_ARG, "decreasing offsets");
+    if (res[0] & 2) return ctx_fail(ctx, SB_E_ARG, "a null list / map slot, or one under a null struct slot, is not empty");
     *last = res[1];
     return SB_OK;
   };
@@ -2543,13 +2567,16 @@ int encode_nested_device(sb_ctx* ctx, const sb_nested_desc* desc, const sb_nest_
       continue;
     }
     if (count[d] / 256 + 1 > 0x7FFFFFFFull) return SB_E_NYI;
-    if (int rc = check(d_nests[d].d_offsets, count[d], &count[d + 1])) return rc;
+    sba::NestDead dead{};
+    for (int u = d; u >= 0 && (u == d || ((desc->struct_mask >> u) & 1)); u--)
+      if (desc->list_nullable[u]) dead.bm[dead.n++] = d_nests[u].d_validity;
+    if (int rc = check(d_nests[d].d_offsets, count[d], dead, &count[d + 1])) return rc;
   }
   const uint64_t n_leaf = count[depth];
   if (binary) {
     uint64_t last = 0;
     if (n_leaf / 256 + 1 > 0x7FFFFFFFull) return SB_E_NYI;
-    if (int rc = check(d_leaf_offsets, n_leaf, &last)) return rc;
+    if (int rc = check(d_leaf_offsets, n_leaf, sba::NestDead{}, &last)) return rc;
     if (last > values_len) return ctx_fail(ctx, SB_E_ARG, "leaf offsets past the values");
   }
   // 2. bottom-up: the level prefixes C_d (nullptr = the identity)

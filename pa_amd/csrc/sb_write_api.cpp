@@ -213,6 +213,12 @@ sb_status sb_encode_list_column(int32_t phys, const int64_t* h_offsets, const ui
   if (!h_out || !out_len || !h_metas || !n_pages || !h_offsets || (n_rows && h_offsets[n_rows] > h_offsets[0] && !h_child))
     return SB_E_ARG;
   if (!sb::enc::type_size(phys)) return SB_E_NYI;
+  if (list_nullable && h_list_validity) {  // a null slot emits one level and no leaf slot: it must be empty
+    uint32_t dead = 0;
+    for (uint64_t i = 0; i < n_rows; i++)
+      dead |= (uint32_t)(h_offsets[i + 1] > h_offsets[i]) & ~(uint32_t)(h_list_validity[i >> 3] >> (i & 7)) & 1u;
+    if (dead) return SB_E_ARG;
+  }
   const uint64_t step = max_page_rows ? std::min<uint64_t>(max_page_rows, n_rows) : n_rows;
   const uint64_t np = step ? (n_rows + step - 1) / step : 0;
   std::vector<std::vector<uint8_t>> pages(np);
@@ -269,7 +275,8 @@ sb_status sb_encode_list_column(int32_t phys, const int64_t* h_offsets, const ui
 // to_nested + to_leaves, slice_parquet_array per page of max_page_rows
 // top-level rows; write_nested serialize.rs:135-198).  The nests' offsets
 // must be non-decreasing over the entries the rows reach (SB_E_ARG
-// otherwise: slice_parquet_array would read past the child arrays).
+// otherwise: slice_parquet_array would read past the child arrays), and a
+// dead list / map slot must be empty (include/strawboat_gpu.h).
 sb_status sb_encode_nested_column(const sb_nested_desc* desc, const sb_nest_in* h_nests, const void* h_values,
                                   const int64_t* h_leaf_offsets, uint64_t values_len, const uint8_t* h_leaf_validity,
                                   uint64_t n_rows, const sb_write_options* opts, uint64_t max_page_rows,
@@ -287,14 +294,27 @@ sb_status sb_encode_nested_column(const sb_nested_desc* desc, const sb_nest_in* 
     nests[d] = sb::enc::NestLevel{h_nests[d].h_offsets, h_nests[d].h_validity, desc->list_nullable[d] != 0, is_struct};
     if (is_struct) continue;
     const int64_t* o = h_nests[d].h_offsets;
-    if (!o) return SB_E_ARG;
-    for (uint64_t i = 0; i < count; i++)
-      if (o[i + 1] < o[i] || o[i] < 0) return SB_E_ARG;
+    if (!o || o[0] < 0) return SB_E_ARG;
+    // a dead slot -- null itself, or null in a struct of the run of structs directly
+    // above -- emits one level and no leaf slot: it must be empty (the leaf slice is
+    // taken through the offsets)
+    const uint8_t* dead[SB_MAX_NEST];
+    int nd = 0;
+    for (int u = d; u >= 0 && (u == d || ((desc->struct_mask >> u) & 1)); u--)
+      if (desc->list_nullable[u] && h_nests[u].h_validity) dead[nd++] = h_nests[u].h_validity;
+    uint32_t bad = 0;  // (no branch on the data: list lengths and nulls are as good as random)
+    for (uint64_t i = 0; i < count; i++) {
+      const int64_t b = o[i], e = o[i + 1];
+      uint32_t live = 1;
+      for (int k = 0; k < nd; k++) live &= (uint32_t)(dead[k][i >> 3] >> (i & 7));
+      bad |= (uint32_t)(b < 0) | (uint32_t)(e < b) | ((uint32_t)(e > b) & (live ^ 1u));
+    }
+    if (bad) return SB_E_ARG;
     count = (uint64_t)o[count];
   }
   if (count && !h_values) return SB_E_ARG;
   if (binary) {
-    if (!h_leaf_offsets) return SB_E_ARG;
+    if (!h_leaf_offsets || h_leaf_offsets[0] < 0) return SB_E_ARG;
     for (uint64_t i = 0; i < count; i++)
       if (h_leaf_offsets[i + 1] < h_leaf_offsets[i] || h_leaf_offsets[i] < 0) return SB_E_ARG;
     if ((uint64_t)h_leaf_offsets[count] > values_len) return SB_E_ARG;

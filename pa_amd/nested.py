@@ -62,13 +62,17 @@ def encode_list_column(offsets: np.ndarray, child: np.ndarray, list_validity=Non
                        list_nullable: bool = False, item_nullable: bool = False, options=None,
                        n_threads: int = 0) -> Tuple[bytes, List[PageMeta]]:
     """encode_chunk for one List<T> leaf: pages of options.max_page_size
-    top-level rows; PageMeta.num_values = the page's level count."""
+    top-level rows; PageMeta.num_values = the page's level count.  A null
+    slot must be empty (E_ARG otherwise: it emits one level and no leaf
+    slot, while the leaf slice is taken through the offsets)."""
     from .write import WriteOptions, _take
 
     L = _lib()
     options = options or WriteOptions()
     offs = np.ascontiguousarray(offsets, np.int64)
     child = np.ascontiguousarray(child)
+    if list_validity is not None and len(list_validity) < len(offs) - 1:
+        raise N.StrawboatError(N.E_ARG, f"encode_list_column: {len(list_validity)} validity slots for {len(offs) - 1}")
     if len(child) == 0:
         child = np.zeros(1, child.dtype)
     lvb = None if list_validity is None else np.packbits(np.asarray(list_validity, bool), bitorder="little")
@@ -84,6 +88,9 @@ def encode_list_column(offsets: np.ndarray, child: np.ndarray, list_validity=Non
                                  n_threads, ctypes.byref(out), ctypes.byref(olen), ctypes.byref(metas),
                                  ctypes.byref(npg))
     if st:
+        if st == N.E_ARG and lvb is not None and list_nullable and \
+                bool(((offs[1:] > offs[:-1]) & ~np.asarray(list_validity, bool)[:len(offs) - 1]).any()):
+            raise N.StrawboatError(st, "encode_list_column: a null list slot is not empty")
         raise N.StrawboatError(st, "encode_list_column")
     pm = [PageMeta(metas[i].length, metas[i].num_values) for i in range(npg.value)]
     L.sb_free(metas)
@@ -97,7 +104,7 @@ def encode_list_column_device(offsets, child, list_validity=None, child_validity
     positions), child, list_validity (over the rows) and child_validity (over
     the child values) are device tensors; returns (device uint8 tensor of the
     column chunk, page metas), byte-identical to encode_list_column with the
-    same options."""
+    same options.  A null slot must be empty, as there (E_ARG otherwise)."""
     import torch
 
     from .read import resolve_context
@@ -571,16 +578,78 @@ def _bits(v):
     return None if v is None else np.packbits(np.asarray(v, bool), bitorder="little")
 
 
+DEAD_SLOT = "a null list / map slot, or one under a null struct slot, is not empty"
+
+
+def check_host_array(fld: Field, arr: HostArray, what: str = "field", dead=None, dead_slots: bool = True):
+    """check_device_array for a HostArray tree, before its buffers go to C:
+    offsets hold length + 1 entries and end inside the child, struct children
+    hold as many slots as the struct, validities and leaf values cover their
+    slots.  `dead` (bool per slot or None) marks the slots that are null in
+    the run of structs directly above: a list / map slot that is dead, or
+    null itself, emits one level and no leaf slot, so it must be empty
+    (dead_slots=False leaves that rule to the C entry point, which refuses
+    such a slot too).  Raises E_ARG on a mismatch."""
+    n = arr.length
+    what = f"{what}.{fld.name}" if fld.name else what
+    valid = None
+    if arr.validity is not None:
+        if len(arr.validity) < n:
+            _bad(f"{what}: {len(arr.validity)} validity slots for {n}")
+        if fld.nullable and dead_slots:
+            valid = np.asarray(arr.validity[:n], bool)
+    if valid is not None:
+        dead = ~valid if dead is None else (dead | ~valid)
+    if fld.kind == "leaf":
+        v = arr.values
+        if fld.physical_type in _BINARY_TYPES:
+            if not isinstance(v, (tuple, list)) or len(v) != 2:
+                _bad(f"{what}: a Binary / Utf8 leaf is (offsets, bytes)")
+            if len(v[0]) < n + 1:
+                _bad(f"{what}: {len(v[0])} leaf offsets for {n} slots")
+            if int(v[0][n]) > len(v[1]):
+                _bad(f"{what}: leaf offsets end past the bytes")
+        elif len(v) < n:
+            _bad(f"{what}: {len(v)} values for {n} slots")
+        return
+    if fld.kind == "struct":
+        if len(arr.children) != len(fld.children):
+            _bad(f"{what}: {len(arr.children)} children for {len(fld.children)} fields")
+        for f, c in zip(fld.children, arr.children):
+            if c.length != n:
+                _bad(f"{what}: a struct child of {c.length} slots under {n}")
+            check_host_array(f, c, what, dead, dead_slots)
+        return
+    if arr.offsets is None or len(arr.offsets) < n + 1:
+        _bad(f"{what}: {0 if arr.offsets is None else len(arr.offsets)} offsets for {n} slots")
+    if len(arr.children) != 1:
+        _bad(f"{what}: a list / map has one child")
+    o = np.asarray(arr.offsets[:n + 1], np.int64)
+    if int(o[n]) > arr.children[0].length:
+        _bad(f"{what}: offsets end past the child's {arr.children[0].length} slots")
+    if dead_slots and dead is not None and bool((dead & (o[1:] > o[:-1])).any()):
+        _bad(f"{what}: {DEAD_SLOT} (slot {int(np.flatnonzero(dead & (o[1:] > o[:-1]))[0])})")
+    check_host_array(fld.children[0], arr.children[0], what, None, dead_slots)
+
+
 def encode_field(fld: Field, arr: HostArray, options=None, n_threads: int = 0):
     """encode_chunk for one nested field (write/common.rs:60-115): one
     column chunk per leaf, to_leaves order, each paged by
     options.max_page_size top-level rows (slice_parquet_array) and written
     by write_nested (serialize.rs:135-198) through the host encoder
-    (sb_encode_nested_column).  Returns [(chunk bytes, [PageMeta])]."""
+    (sb_encode_nested_column).  Returns [(chunk bytes, [PageMeta])].
+
+    Any legal Arrow array is written as its logical value (valid children
+    under a null struct slot, offsets that start above 0, children longer
+    than the offsets reach, a nullable nest with validity None), but one: a
+    list / map slot that is null, or under a null slot of the run of structs
+    directly above it, must be empty -- E_ARG otherwise, as for buffers
+    shorter than their slot counts (check_host_array)."""
     from .write import WriteOptions, _take
 
     if fld.kind == "leaf":
         raise N.StrawboatError(N.E_ARG, "a primitive field is not nested: use encode_column")
+    check_host_array(fld, arr, dead_slots=False)  # the buffer lengths, before C reads them
     L = _encode_lib()
     options = options or WriteOptions()
     opts = options.c()
@@ -631,6 +700,8 @@ def encode_field(fld: Field, arr: HostArray, options=None, n_threads: int = 0):
                                        ctypes.byref(opts), options.max_page_size or 0, n_threads, ctypes.byref(out),
                                        ctypes.byref(olen), ctypes.byref(metas), ctypes.byref(npg))
         if st:
+            if st == N.E_ARG:
+                check_host_array(fld, arr)  # names a dead slot that is not empty
             raise N.StrawboatError(st, "encode_nested_column")
         pm = [PageMeta(metas[i].length, metas[i].num_values) for i in range(npg.value)]
         L.sb_free(metas)
@@ -769,7 +840,10 @@ def encode_field_device(fld: Field, arr: DeviceArray, options=None, ctx=None):
     int32 or int64; a Binary / Utf8 leaf's values length is the bytes its
     slots span.  Returns [(device uint8 chunk, [PageMeta])], one per leaf in
     to_leaves order, byte-identical to encode_field (a Zstd default codec:
-    the device's own frames)."""
+    the device's own frames).  As encode_field, it refuses (E_ARG) a list /
+    map slot with children that is null or under a null slot of the run of
+    structs directly above it: the offsets check of each nest (k_nest_check)
+    reads those bitmaps before any page is written."""
     import torch
 
     from .write import WriteOptions, pack_bits, page_rows, run_device_encode

@@ -1254,6 +1254,26 @@ fn check_offsets(offsets: &[i64], n: u64, limit: u64) -> Result<()> {
     Ok(())
 }
 
+/// The list / map nest `d` of a leaf path holds no dead slot with children.  A
+/// slot is dead if it is null itself, or null in a struct of the run of struct
+/// nests directly above (a struct passes its slot index through).  A dead slot
+/// emits one level and no leaf slot, while the leaf slice is taken through the
+/// offsets: its children's values would be written with no level to pair them.
+fn check_dead_slots(name: &str, nests: &[(&HostArray, Nest)], d: usize, offsets: &[i64]) -> Result<()> {
+    let bitmaps: Vec<&Vec<u8>> = (0..=d)
+        .rev()
+        .take_while(|&u| u == d || nests[u].1.is_struct)
+        .filter(|&u| nests[u].1.nullable)
+        .filter_map(|u| nests[u].0.validity().as_ref())
+        .collect();
+    for (i, w) in offsets.windows(2).enumerate() {
+        if w[1] > w[0] && bitmaps.iter().any(|b| (b[i >> 3] >> (i & 7)) & 1 == 0) {
+            return Err(arg(format!("{name}: slot {i} of nest {d} is null, or under a null struct slot, and not empty")));
+        }
+    }
+    Ok(())
+}
+
 /// One leaf of a nested array: the arrays on its path (outermost first,
 /// each with its nest), the leaf array and its field.
 struct LeafArrays<'a> {
@@ -1348,6 +1368,7 @@ fn encode_nested_leaf(top_len: u64, l: &LeafArrays, o: &WriteOptions) -> Result<
             HostArray::Struct { .. } => desc.struct_mask |= 1 << d,
             HostArray::List { offsets, values: child, .. } | HostArray::Map { offsets, field: child, .. } => {
                 check_offsets(offsets, count, child.len())?;
+                check_dead_slots(name, &l.nests, d, offsets)?;
                 nests[d].h_offsets = offsets.as_ptr();
                 count = child.len();
             }

@@ -8,7 +8,16 @@ Children of a null struct / list slot are null where they are nullable
 are not (`pa.array([None], struct)` keeps valid children), and arrow2's
 level writer (RepLevelsIter / DefLevelsIter) reads the children's own
 validity under a null struct, so only such arrays round-trip through the
-reference writer."""
+reference writer.
+
+That normal form (gen, io_rs_cases: a null list / map slot empty, children
+of a null struct slot null, lists under it empty, offsets from 0) is more
+than the writers here ask for.  Their contract: a slot is dead if it is
+null itself, or null in a struct of the run of structs directly above it; a
+dead list / map slot with children is refused (SB_E_ARG); every other legal
+Arrow array is written as its logical value.  gen(loose=True), sliced and
+with_dead_children build the arrays outside the normal form, logical() is
+their value in it (pinned against pyarrow's to_pylist())."""
 from __future__ import annotations
 
 import numpy as np
@@ -38,14 +47,19 @@ def map_(key, value, nullable, name=""):
     return F("map", nullable, [struct([key, value], False, "entries")], name=name)
 
 
-def gen(f: F, n: int, rng, parent_valid=None, null_density=0.2, uniq=None) -> A:
+def gen(f: F, n: int, rng, parent_valid=None, null_density=0.2, uniq=None, loose=False) -> A:
     """A random array of field f with n slots; parent_valid (bool per slot
-    or None) nulls the nullable children of null parents."""
+    or None) nulls the nullable children of null parents.  loose: children
+    under a null struct slot keep their own random validity instead (legal
+    Arrow, and what pa.array([None], struct) builds); lists under such a slot
+    stay empty, valid or not."""
     pv = np.ones(n, bool) if parent_valid is None else parent_valid
     validity = None
     if f.nullable:
-        validity = (rng.random(n) >= null_density) & pv
-    live = pv if validity is None else validity
+        validity = rng.random(n) >= null_density
+        if not loose:
+            validity &= pv
+    live = pv if validity is None else (validity & pv)
     if f.kind == "leaf":
         if f.leaf == "fixed":
             dt = f.dtype
@@ -63,13 +77,13 @@ def gen(f: F, n: int, rng, parent_valid=None, null_density=0.2, uniq=None) -> A:
         offs[1:] = np.cumsum([len(s) for s in strs])
         return A("leaf", n, validity, values=(offs, b"".join(strs)))
     if f.kind == "struct":
-        kids = [gen(c, n, rng, live, null_density, uniq) for c in f.children]
+        kids = [gen(c, n, rng, live, null_density, uniq, loose) for c in f.children]
         return A("struct", n, validity, children=kids)
     # list / map: lengths uniform {0, 1, 2} (io.rs:399-415), null / dead slots empty
     lens = np.where(live, rng.integers(0, 3, n), 0)
     offs = np.zeros(n + 1, np.int64)
     offs[1:] = np.cumsum(lens)
-    child = gen(f.children[0], int(offs[-1]), rng, None, null_density, uniq)
+    child = gen(f.children[0], int(offs[-1]), rng, None, null_density, uniq, loose)
     return A(f.kind, n, validity, offsets=offs, children=[child])
 
 
@@ -295,3 +309,199 @@ def compact(a: A) -> A:
     Arrow logical equality compares, e.g. io.rs's ListArray over the first
     half of a longer child)."""
     return _slice(a, 0, a.length)
+
+
+# ---- loose arrays: legal Arrow outside the normal form of gen() ---------------
+def _gather(f: F, a: A, idx, dead) -> A:
+    """Slots idx of a as their logical value: dead (bool per taken slot or
+    None) marks the slots that are null in the run of structs directly above."""
+    idx = np.asarray(idx, np.int64)
+    v = None if a.validity is None else np.asarray(a.validity, bool)[idx]
+    if f.nullable and dead is not None:
+        v = ~dead if v is None else (v & ~dead)
+    if f.nullable and v is not None:
+        dead = ~v if dead is None else (dead | ~v)
+    if f.kind == "leaf":
+        if f.leaf == "binary":
+            o, data = a.values
+            strs = [bytes(data[int(o[i]):int(o[i + 1])]) for i in idx]
+            offs = np.zeros(len(idx) + 1, np.int64)
+            offs[1:] = np.cumsum([len(x) for x in strs])
+            return A("leaf", len(idx), v, values=(offs, b"".join(strs)))
+        return A("leaf", len(idx), v, values=np.asarray(a.values)[idx])
+    if f.kind == "struct":
+        return A("struct", len(idx), v, children=[_gather(c, x, idx, dead) for c, x in zip(f.children, a.children)])
+    o = np.asarray(a.offsets, np.int64)
+    lens = o[idx + 1] - o[idx]
+    if dead is not None:
+        lens = np.where(dead, 0, lens)
+    offs = np.zeros(len(idx) + 1, np.int64)
+    offs[1:] = np.cumsum(lens)
+    cidx = np.concatenate([np.arange(o[i], o[i] + n) for i, n in zip(idx, lens)] + [np.zeros(0, np.int64)])
+    return A(f.kind, len(idx), v, offsets=offs, children=[_gather(f.children[0], a.children[0], cidx, None)])
+
+
+def logical(f: F, a: A) -> A:
+    """The logical Arrow value of a (what pyarrow's to_pylist() shows), in the
+    normal form of gen(): compact(a) with the nullable children of dead
+    struct slots null, dead lists empty and every offsets buffer rebased to 0.
+    A slot is dead if it is null, or null in a struct of the run of structs
+    directly above it.  The reference of the loose-array tests: no writer
+    of ours takes part in it."""
+    return _gather(f, a, np.arange(a.length), None)
+
+
+def _concat(f: F, parts) -> A:
+    """The arrays one after the other (offsets shifted onto the joined
+    child); each part's offsets span its whole child, as gen()'s do."""
+    n = sum(x.length for x in parts)
+    v = None
+    if any(x.validity is not None for x in parts):
+        v = np.concatenate([np.ones(x.length, bool) if x.validity is None else np.asarray(x.validity, bool)[:x.length]
+                            for x in parts])
+    if f.kind == "leaf":
+        if f.leaf == "binary":
+            offs, base = [np.zeros(0, np.int64)], 0
+            for x in parts:
+                o, data = x.values
+                offs.append(np.asarray(o, np.int64)[:x.length] + base)
+                base += len(data)
+            last = parts[-1]
+            end = base - len(last.values[1]) + int(last.values[0][last.length])
+            return A("leaf", n, v, values=(np.concatenate(offs + [np.array([end], np.int64)]),
+                                           b"".join(bytes(x.values[1]) for x in parts)))
+        return A("leaf", n, v, values=np.concatenate([np.asarray(x.values)[:x.length] for x in parts]))
+    if f.kind == "struct":
+        return A("struct", n, v, children=[_concat(c, [x.children[k] for x in parts]) for k, c in enumerate(f.children)])
+    offs, base = [], 0
+    for x in parts:
+        offs.append(np.asarray(x.offsets, np.int64)[:x.length] + base)
+        base += x.children[0].length
+    last = parts[-1]
+    end = base - last.children[0].length + int(last.offsets[last.length])
+    return A(f.kind, n, v, offsets=np.concatenate(offs + [np.array([end], np.int64)]),
+             children=[_concat(f.children[0], [x.children[0] for x in parts])])
+
+
+def sliced(f: F, a: A, k: int) -> A:
+    """The same logical array as a slice of longer buffers: k junk slots
+    before every list / map child and k junk bytes before every Binary
+    leaf's bytes (the offsets raised to match, so offsets[0] > 0), and k
+    unreachable slots behind every list / map child."""
+    rng = np.random.default_rng(1000 + k)
+    if f.kind == "leaf":
+        if f.leaf != "binary":
+            return a
+        o, data = a.values
+        return A("leaf", a.length, a.validity, values=(np.asarray(o, np.int64) + k, bytes(rng.integers(97, 123, k, np.uint8)) + bytes(data)))
+    if f.kind == "struct":
+        return A("struct", a.length, a.validity, children=[sliced(c, x, k) for c, x in zip(f.children, a.children)])
+    cf = f.children[0]
+    # (the junk goes on first: offsets cannot leave a gap between two slots, so _concat wants whole children)
+    child = sliced(cf, _concat(cf, [gen(cf, k, rng), a.children[0], gen(cf, k, rng)]), k)
+    return A(f.kind, a.length, a.validity, offsets=np.asarray(a.offsets, np.int64) + k, children=[child])
+
+
+def _insert(f: F, a: A, slot: int, rng) -> A:
+    """List / map array a with one more (random) child in `slot`."""
+    cf, c = f.children[0], a.children[0]
+    o = np.asarray(a.offsets, np.int64).copy()
+    p = int(o[slot + 1])
+    o[slot + 1:] += 1
+    child = _concat(cf, [_slice(c, 0, p), gen(cf, 1, rng), _slice(c, p, c.length)])
+    return A(a.kind, a.length, a.validity, offsets=o, children=[child])
+
+
+def loose_shapes():
+    """name -> field of the loose-array tests: shapes() and three list leaves."""
+    return {**shapes(),
+            "list_bool": lst(leaf("bool", True, "item"), True),
+            "list_utf8": lst(leaf("utf8", True, "item"), True),
+            "list_list_i32": lst(lst(leaf("i32", True, "item"), True, "item"), True)}
+
+
+def loose_array(name: str, n: int = 300, k: int = 3):
+    """-> (field, a loose array of it): gen(loose=True) as a slice (k > 0)."""
+    f = loose_shapes()[name]
+    a = gen(f, n, np.random.default_rng(70 + list(loose_shapes()).index(name)), loose=True)
+    return f, sliced(f, a, k) if k else a
+
+
+DEAD_WHERE = ("top", "inner", "under_null_struct", "under_struct_under_null_struct")
+DEAD_ROWS = (0, 15, 16, 21, 63)  # of 64 rows in pages of 16: the first row, both sides of a page edge, inside, the last
+
+
+def dead_fields():
+    """name -> (field, where) of the refusal tests."""
+    ints = lambda name="": lst(leaf("i32", True, "item"), True, name)  # noqa: E731
+    return {
+        "top_list": (ints(), "top"),
+        "top_map": (shapes()["map"], "top"),
+        "inner": (lst(ints("item"), True), "inner"),
+        "under_null_struct": (struct([ints("l"), leaf("i32", True, "x")], True), "under_null_struct"),
+        "under_struct_under_null_struct": (struct([struct([ints("l")], False, "s"), leaf("i32", True, "x")], True),
+                                           "under_struct_under_null_struct"),
+    }
+
+
+def dead_case(name: str, row: int):
+    """-> (field, bad, twin) of with_dead_children over 64 rows."""
+    f, where = dead_fields()[name]
+    a = gen(f, 64, np.random.default_rng(90 + list(dead_fields()).index(name)))
+    return (f,) + with_dead_children(f, a, where, row)
+
+
+def with_dead_children(f: F, a: A, where: str, row: int):
+    """-> (bad, twin).  bad: a (an array of gen()) with one dead list / map
+    slot holding one child -- `top`: slot `row` of a nullable list / map f is
+    null; `inner`: the first inner list of row `row` of a List<List<>> is
+    null; `under_null_struct`: slot `row` of the nullable struct f is null and
+    its first list child holds a child there (the list slot itself valid);
+    `under_struct_under_null_struct`: the same with a required struct
+    between them.  twin: the same array with that one range empty, which every
+    writer must take."""
+    rng = np.random.default_rng(row)
+    assert where in DEAD_WHERE
+
+    def kill(x, i):
+        v = np.ones(x.length, bool) if x.validity is None else np.asarray(x.validity, bool).copy()
+        v[i] = False
+        return A(x.kind, x.length, v, x.offsets, x.children, x.values)
+
+    if where == "top":
+        assert f.kind != "struct" and f.nullable
+        twin = logical(f, kill(a, row))
+        return _insert(f, twin, row, rng), twin
+    if where == "inner":
+        cf = f.children[0]
+        assert f.kind != "struct" and cf.kind not in ("struct", "leaf") and cf.nullable
+        if a.validity is not None:
+            a = A(a.kind, a.length, np.asarray(a.validity, bool).copy(), a.offsets, a.children)
+            a.validity[row] = True
+        if a.offsets[row + 1] == a.offsets[row]:
+            a = _insert(f, a, row, rng)
+        j = int(a.offsets[row])
+        twin = logical(f, A(a.kind, a.length, a.validity, a.offsets, [kill(a.children[0], j)]))
+        j = int(twin.offsets[row])
+        return A(twin.kind, twin.length, twin.validity, twin.offsets, [_insert(cf, twin.children[0], j, rng)]), twin
+    # the first list / map child of the struct f, one or two structs down
+    depth = 1 if where == "under_null_struct" else 2
+    assert f.kind == "struct" and f.nullable
+    twin = logical(f, kill(a, row))
+
+    def descend(g, x, d, edit):
+        want = (lambda c: c.kind not in ("struct", "leaf")) if d == 1 else (lambda c: c.kind == "struct")
+        k = next(i for i, c in enumerate(g.children) if want(c))
+        kids = list(x.children)
+        kids[k] = edit(g.children[k], kids[k]) if d == 1 else descend(g.children[k], kids[k], d - 1, edit)
+        return A(x.kind, x.length, x.validity, x.offsets, kids, x.values)
+
+    def valid_there(g, x):  # the list slot itself stays valid: only the struct above it is null
+        if x.validity is None:
+            return x
+        v = np.asarray(x.validity, bool).copy()
+        v[row] = True
+        return A(x.kind, x.length, v, x.offsets, x.children)
+
+    twin = descend(f, twin, depth, valid_there)
+    return descend(f, twin, depth, lambda g, x: _insert(g, x, row, rng)), twin
