@@ -249,6 +249,56 @@ sb_status sb_decode_nested_planned(sb_ctx* ctx, sb_plan* plan, const sb_nested_o
  * status (SB_OK if every page decoded); *h_bad_page = its index or -1. */
 sb_status sb_plan_status(sb_ctx* ctx, sb_plan* plan, int64_t* h_bad_page);
 
+/* ---- selective reads ----------------------------------------------------
+ * A selection is an LSB-first Arrow bitmap in HBM over a flat column's rows:
+ * bit i set = row i is wanted.  A selective plan decodes exactly the selected
+ * rows, in row order, as dense Arrow buffers (values, validity, for Binary /
+ * Utf8 offsets that start at 0).  Pages without a selected row are never
+ * read: they need not be uploaded (packed = 1) and are not planned, staged
+ * or decoded; a Utf8 column is therefore validated on its touched pages
+ * only.  Flat leaves only (fixed width, Boolean, Binary / Utf8 / Large*):
+ * selecting rows of a nested leaf needs per-level compaction of its offsets
+ * and is not implemented (the callers' SB_E_NYI). */
+typedef struct sb_select sb_select;
+/* Resolves a selection against a column's pages (synchronous: k_sel_count +
+ * one readback of 8 bytes per page).  d_selection: 4*ceil(n_rows/32) readable
+ * bytes, 4-byte aligned, bits past n_rows ignored; it stays alive and
+ * unchanged while the sb_select and the plans made from it exist.
+ * SB_E_ARG if sum(num_values) != n_rows. */
+sb_status sb_select_create(sb_ctx* ctx, const uint8_t* d_selection, uint64_t n_rows, const sb_page_meta* h_metas,
+                           uint64_t n_pages, sb_select** out);
+uint64_t sb_select_num_rows(const sb_select* sel);  /* selected rows */
+uint64_t sb_select_num_pages(const sb_select* sel); /* touched pages */
+/* The i-th touched page (ascending): its index in the column and its selected rows. */
+sb_status sb_select_page(const sb_select* sel, uint64_t i, uint64_t* page_index, uint64_t* selected);
+void sb_select_destroy(sb_select* sel);
+
+/* Plans the touched pages only.  packed = 0: d_chunk is the whole column
+ * chunk, pages at their running byte offsets.  packed = 1: d_chunk holds only
+ * the touched pages, back to back (what a file read that skipped the rest
+ * uploaded).  The plan copies what it needs from sel (which may be destroyed).
+ * On the plan: sb_plan_num_rows = the selected rows, sb_plan_num_pages = the
+ * touched pages, sb_plan_values_bytes = the touched pages' values bytes (the
+ * capacity a caller allocates for Binary values), sb_plan_status reports the
+ * first failing page by its index in the column; sb_plan_destroy frees the
+ * plan's scratch.  Fixed width / Boolean: fully selected pages decode
+ * straight into the outputs at their compacted row base, partially selected
+ * ones into plan-owned scratch and through k_sel_take.  Binary / Utf8: every
+ * touched page decodes into scratch, then k_sel_take_bin. */
+sb_status sb_plan_selected_column(sb_ctx* ctx, const sb_column_desc* desc, const sb_select* sel, const uint8_t* d_chunk,
+                                  uint64_t chunk_len, int32_t packed, sb_plan** out);
+/* Asynchronous decodes of a selective plan.  Outputs as sb_primitive_out /
+ * sb_binary_out over sb_plan_num_rows rows; values under null slots are the
+ * bytes the page decoded to.  No row selected: nothing is launched (Binary:
+ * offsets[0] = 0). */
+sb_status sb_decode_selected(sb_ctx* ctx, sb_plan* plan, const sb_primitive_out* out);
+sb_status sb_decode_binary_selected(sb_ctx* ctx, sb_plan* plan, const sb_binary_out* out);
+/* After a decode (waits for it): the values bytes it wrote. */
+sb_status sb_plan_selected_values_bytes(sb_ctx* ctx, sb_plan* plan, uint64_t* bytes);
+/* Touched pages decoded in place / through scratch, and the plan's scratch bytes. */
+sb_status sb_plan_selected_stats(const sb_plan* plan, uint64_t* pages_direct, uint64_t* pages_compacted,
+                                 uint64_t* scratch_bytes);
+
 /* ---- page-level unit entry points (synchronous) -------------------------
  * For a caller that walks the pages itself; the column decoders above fuse
  * both steps into their page kernels.

@@ -34,6 +34,9 @@ EXPORTED = [
     "sb_decode_page_validity", "sb_decode_page_levels", "sb_plan_column_at",
     "sb_encode_list_device_bound", "sb_encode_list_column_device", "sb_encode_nested_column",
     "sb_encode_nested_device_bound", "sb_encode_nested_column_device",
+    "sb_select_create", "sb_select_num_rows", "sb_select_num_pages", "sb_select_page", "sb_select_destroy",
+    "sb_plan_selected_column", "sb_decode_selected", "sb_decode_binary_selected", "sb_plan_selected_values_bytes",
+    "sb_plan_selected_stats",
 ]
 
 MAX_NEST = 4
@@ -183,5 +186,26 @@ def lib():
     L.sb_file_schema.restype = I32
     L.sb_file_upload.argtypes = [P, P, U64, U64, P]
     L.sb_file_upload.restype = I32
+    PU64 = ctypes.POINTER(U64)
+    L.sb_select_create.argtypes = [P, P, U64, ctypes.POINTER(PageMetaC), U64, PP]
+    L.sb_select_create.restype = I32
+    L.sb_select_num_rows.argtypes = [P]
+    L.sb_select_num_rows.restype = U64
+    L.sb_select_num_pages.argtypes = [P]
+    L.sb_select_num_pages.restype = U64
+    L.sb_select_page.argtypes = [P, U64, PU64, PU64]
+    L.sb_select_page.restype = I32
+    L.sb_select_destroy.argtypes = [P]
+    L.sb_select_destroy.restype = None
+    L.sb_plan_selected_column.argtypes = [P, ctypes.POINTER(ColumnDescC), P, P, U64, I32, PP]
+    L.sb_plan_selected_column.restype = I32
+    L.sb_decode_selected.argtypes = [P, P, ctypes.POINTER(PrimitiveOutC)]
+    L.sb_decode_selected.restype = I32
+    L.sb_decode_binary_selected.argtypes = [P, P, P]  # (sb_binary_out: pa_amd.binary.BinaryOutC, by reference)
+    L.sb_decode_binary_selected.restype = I32
+    L.sb_plan_selected_values_bytes.argtypes = [P, P, PU64]
+    L.sb_plan_selected_values_bytes.restype = I32
+    L.sb_plan_selected_stats.argtypes = [P, PU64, PU64, PU64]
+    L.sb_plan_selected_stats.restype = I32
     _lib = L
     return L

@@ -152,6 +152,16 @@ class BinaryColumnDecoder:
         dec.shard = shard
         return dec
 
+    @classmethod
+    def select(cls, chunk, page_metas, physical_type: int = UTF8, nullable: bool = False, selection=None, ctx=None,
+               packed: bool = False):
+        """ColumnDecoder.select for Binary / Utf8: decode() returns the selected
+        rows' offsets (from 0), the values narrowed to the bytes written, and
+        the validity.  Utf8 is validated on the touched pages only."""
+        from .select import SelectedBinaryDecoder
+
+        return SelectedBinaryDecoder(chunk, page_metas, physical_type, nullable, selection, ctx, packed)
+
     def alloc_outputs(self):
         torch = self._torch
         dev = f"cuda:{self.ctx.device}"

@@ -54,6 +54,8 @@ int ctx_fail(sb_ctx* c, int st, const char* what, int hip_error) {
 }
 }  // namespace sb
 
+struct SelState;  // a selective-read plan's pages, inner plans and scratch (below)
+
 struct sb_plan {
   sb_column_desc desc{};
   const uint8_t* d_chunk = nullptr;
@@ -111,6 +113,7 @@ struct sb_plan {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timing = false;  // record HIP events around each decode (sb_plan_enable_timing)
   bool timed = false;
+  SelState* sel = nullptr;  // sb_plan_selected_column: decoded by sb_decode_selected / sb_decode_binary_selected
 };
 
 // k_inflate claims from one of the plan's two counter pairs and zeroes the
@@ -216,6 +219,9 @@ sb_status sb_sync(sb_ctx* ctx) {
 
 const char* sb_last_error(const sb_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
+static void sel_destroy(SelState* s);
+static sb_status sel_status(sb_ctx* ctx, sb_plan* p, int64_t* bad);
+
 void sb_plan_destroy(sb_plan* p) {
   if (!p) return;
   if (p->d_pages) (void)hipFree(p->d_pages);
@@ -235,6 +241,7 @@ void sb_plan_destroy(sb_plan* p) {
   if (p->d_lc) (void)hipFree(p->d_lc);
   if (p->d_nest) (void)hipFree(p->d_nest);
   if (p->inner) sb_plan_destroy(p->inner);
+  if (p->sel) sel_destroy(p->sel);
   if (p->ev0) (void)hipEventDestroy(p->ev0);
   if (p->ev1) (void)hipEventDestroy(p->ev1);
   delete p;
@@ -253,8 +260,11 @@ uint64_t sb_plan_num_pages(const sb_plan* p) { return p ? p->n_pages : 0; }
 // at decode time).
 enum RegionMode { kRegionsNone = 0, kRegionsProbe = 1, kRegionsBySize = 2 };
 
+// ids: the index each page is reported by (a selective read's touched pages
+// keep their index in the column), nullptr = its position in `pages`.
 static sb_status plan_pages(sb_ctx* ctx, const sb_column_desc* desc, const uint8_t* d_chunk, uint64_t chunk_len,
-                            std::vector<sb::PageDesc> pages, sb_plan** out, int regions = kRegionsProbe);
+                            std::vector<sb::PageDesc> pages, sb_plan** out, int regions = kRegionsProbe,
+                            const uint32_t* ids = nullptr);
 
 static sb_status plan_column(sb_ctx* ctx, const sb_column_desc* desc, const uint8_t* d_chunk, uint64_t chunk_len,
                              const sb_page_meta* h_metas, uint64_t n_pages, sb_plan** out, int regions);
@@ -392,7 +402,7 @@ static hipError_t plan_bool_regions(sb_ctx* ctx, sb_plan* p, std::vector<sb::Pag
 }
 
 static sb_status plan_pages(sb_ctx* ctx, const sb_column_desc* desc, const uint8_t* d_chunk, uint64_t chunk_len,
-                            std::vector<sb::PageDesc> pages, sb_plan** out, int regions) {
+                            std::vector<sb::PageDesc> pages, sb_plan** out, int regions, const uint32_t* ids) {
   const uint64_t n_pages = pages.size();
   bool is_float;
   int width = type_width(desc->physical_type, &is_float);
@@ -412,7 +422,7 @@ static sb_status plan_pages(sb_ctx* ctx, const sb_column_desc* desc, const uint8
     const sb::PageDesc& pd = pages[i];
     const sb_page_meta m{pd.byte_len, pd.num_values};
     if (pd.byte_off + m.length > chunk_len)
-      return fail(ctx, SB_E_ARG, "page %llu overruns the column chunk", (unsigned long long)i);
+      return fail(ctx, SB_E_ARG, "page %llu overruns the column chunk", (unsigned long long)(ids ? ids[i] : i));
     // a 32-bit validity word shared by two pages is merged with atomics
     if ((pd.row_off & 31) || (m.num_values & 31)) needs_zero = true;
     if (is_bool)  // page + its expanded bitmap, as k_bool_decode lays them out in LDS (big pages: all of it)
@@ -610,7 +620,8 @@ static sb_status plan_pages(sb_ctx* ctx, const sb_column_desc* desc, const uint8
     for (uint64_t i = 0; i < n_pages; i++) {
       if (st[i]) {
         sb_plan_destroy(p);
-        return fail(ctx, (sb_status)st[i], "page %llu: %s", (unsigned long long)i, sb_status_str((int)st[i]));
+        return fail(ctx, (sb_status)st[i], "page %llu: %s", (unsigned long long)(ids ? ids[i] : i),
+                    sb_status_str((int)st[i]));
       }
     }
     if (p->n_bin_jobs && hipMalloc(&p->d_scratch, (rows + n_pages) * (uint64_t)owidth) != hipSuccess) {
@@ -648,6 +659,7 @@ uint64_t sb_plan_values_bytes(const sb_plan* p) { return p ? p->values_bytes : 0
 
 sb_status sb_decode_binary_planned(sb_ctx* ctx, sb_plan* p, const sb_binary_out* out) {
   if (!ctx || !p || !out) return fail(ctx, SB_E_ARG, "null argument");
+  if (p->sel) return fail(ctx, SB_E_ARG, "selective plan: use sb_decode_binary_selected");
   if (!p->binary) return fail(ctx, SB_E_ARG, "not a binary plan");
   if (!out->d_offsets || (p->values_bytes && (!out->d_values || out->values_capacity < p->values_bytes)))
     return fail(ctx, SB_E_ARG, "binary output buffers too small");
@@ -714,6 +726,7 @@ sb_status sb_decode_binary_planned(sb_ctx* ctx, sb_plan* p, const sb_binary_out*
 
 sb_status sb_decode_planned(sb_ctx* ctx, sb_plan* p, const sb_primitive_out* out) {
   if (!ctx || !p || !out) return fail(ctx, SB_E_ARG, "null argument");
+  if (p->sel) return fail(ctx, SB_E_ARG, "selective plan: use sb_decode_selected");
   if (p->binary) return fail(ctx, SB_E_ARG, "binary plan: use sb_decode_binary_planned");
   if (p->n_rows && !out->d_values) return fail(ctx, SB_E_ARG, "values buffer is null");
   if (p->desc.nullable && p->n_rows && !out->d_validity) return fail(ctx, SB_E_ARG, "validity buffer is null");
@@ -811,6 +824,7 @@ sb_status sb_decode_planned(sb_ctx* ctx, sb_plan* p, const sb_primitive_out* out
 
 sb_status sb_plan_status(sb_ctx* ctx, sb_plan* p, int64_t* bad) {
   if (!ctx || !p) return fail(ctx, SB_E_ARG, "null argument");
+  if (p->sel) return sel_status(ctx, p, bad);
   if ((p->list || p->nested) && p->inner) {  // levels first, then the values streams
     const bool l = p->list, n = p->nested;
     p->list = p->nested = false;
@@ -1232,6 +1246,352 @@ sb_status sb_read_meta(const uint8_t* f, uint64_t flen, uint64_t* col_off, uint6
   }
   *n_cols = nc;
   *n_pages = total;
+  return SB_OK;
+}
+
+// ---- selective reads ------------------------------------------------------
+// A selection resolved against a column's pages: which pages hold a selected
+// row (the touched pages) and how many.  Untouched pages never reach a plan:
+// they are not uploaded (packed = 1), not classified, not staged, not decoded.
+struct sb_select {
+  const uint8_t* d_selection = nullptr;
+  uint64_t n_rows = 0, n_selected = 0;
+  std::vector<sb_page_meta> metas;  // the column's pages
+  std::vector<uint64_t> counts;     // selected rows of each
+  std::vector<uint32_t> touched;    // pages with counts > 0, ascending
+};
+
+// Fixed width / Boolean: the fully selected touched pages decode straight
+// into the caller's output at their compacted row base (`direct`, the
+// sb_plan_column_at mechanism), the partially selected ones into `scratch`
+// and through k_sel_take (`part`).  Binary / Utf8 has no placed-page
+// mechanism: every touched page is a `part` page.
+struct SelState {
+  sb_plan* direct = nullptr;
+  sb_plan* part = nullptr;
+  std::vector<uint32_t> direct_ids, part_ids;  // each inner page's index in the column
+  const uint32_t* d_sel = nullptr;
+  uint32_t n_tiles = 0;
+  uint64_t part_rows = 0;                      // rows of the scratch column
+  uint8_t* d_scratch = nullptr;                // one allocation, carved below
+  uint64_t scratch_bytes = 0;
+  sb::SelPage* d_sp = nullptr;
+  uint32_t* d_tiles = nullptr;
+  uint64_t* d_tile_bytes = nullptr;            // binary: [n_tiles + 1]
+  uint8_t* s_values = nullptr;                 // decoded rows of the part pages
+  uint8_t* s_validity = nullptr;
+  uint8_t* s_aux = nullptr;                    // binary: offsets
+  uint64_t s_values_len = 0;
+};
+
+static void sel_destroy(SelState* s) {
+  if (s->direct) sb_plan_destroy(s->direct);
+  if (s->part) sb_plan_destroy(s->part);
+  if (s->d_scratch) (void)hipFree(s->d_scratch);
+  delete s;
+}
+
+static sb_status sel_status(sb_ctx* ctx, sb_plan* p, int64_t* bad) {
+  if (bad) *bad = -1;
+  SelState* s = p->sel;
+  sb_status st = SB_OK;
+  int64_t first = -1;
+  std::string msg;
+  sb_plan* inner[2] = {s->direct, s->part};
+  const std::vector<uint32_t>* ids[2] = {&s->direct_ids, &s->part_ids};
+  for (int k = 0; k < 2; k++) {
+    if (!inner[k]) continue;
+    int64_t b = -1;
+    const sb_status ist = sb_plan_status(ctx, inner[k], &b);
+    if (!ist) continue;
+    if (b < 0) return ist;  // (a device error: the context holds its message)
+    const int64_t col = (int64_t)(*ids[k])[(size_t)b];
+    if (first < 0 || col < first) {
+      first = col;
+      st = ist;
+    }
+  }
+  if (!st) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (no inner plan: nothing else waited)
+    return SB_OK;
+  }
+  if (bad) *bad = first;
+  return fail(ctx, st, "page %lld: %s", (long long)first, sb_status_str((int)st));
+}
+
+sb_status sb_select_create(sb_ctx* ctx, const uint8_t* d_selection, uint64_t n_rows, const sb_page_meta* h_metas,
+                           uint64_t n_pages, sb_select** out) {
+  if (!ctx || !out || (!d_selection && n_rows) || (!h_metas && n_pages)) return SB_E_ARG;
+  if (n_pages > 0xFFFFFFFFull) return fail(ctx, SB_E_ARG, "too many pages");
+  if ((uintptr_t)d_selection % 4) return fail(ctx, SB_E_ARG, "selection bitmap is not 4-byte aligned");
+  std::vector<uint64_t> rows(n_pages + 1, 0);
+  for (uint64_t i = 0; i < n_pages; i++) {
+    if (h_metas[i].length > 0xFFFFFFFFull || h_metas[i].num_values > 0xFFFFFFFFull)
+      return fail(ctx, SB_E_ARG, "page %llu exceeds u32 sizes", (unsigned long long)i);
+    rows[i + 1] = rows[i] + h_metas[i].num_values;
+  }
+  if (rows[n_pages] != n_rows)
+    return fail(ctx, SB_E_ARG, "the pages hold %llu rows, the selection %llu", (unsigned long long)rows[n_pages],
+                (unsigned long long)n_rows);
+  sb_select* s = new sb_select();
+  s->d_selection = d_selection;
+  s->n_rows = n_rows;
+  s->metas.assign(h_metas, h_metas + n_pages);
+  s->counts.assign(n_pages, 0);
+  if (n_pages && n_rows) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint64_t* d = nullptr;  // [row offsets n + 1 | counts n]
+    hipError_t e = hipMalloc(&d, (2 * n_pages + 1) * sizeof(uint64_t));
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(d, rows.data(), (n_pages + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && sb::launch_sel_count((const uint32_t*)d_selection, d, (uint32_t)n_pages, d + n_pages + 1,
+                                                ctx->stream))
+      e = hipErrorLaunchFailure;
+    if (e == hipSuccess)  // the plan's one readback: 8 bytes per page
+      e = hipMemcpyAsync(s->counts.data(), d + n_pages + 1, n_pages * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                         ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (d) (void)hipFree(d);
+    if (e != hipSuccess) {
+      delete s;
+      return fail(ctx, SB_E_DEVICE, "selection count: %s", hipGetErrorString(e));
+    }
+  }
+  for (uint64_t i = 0; i < n_pages; i++) {
+    if (!s->counts[i]) continue;
+    s->touched.push_back((uint32_t)i);
+    s->n_selected += s->counts[i];
+  }
+  *out = s;
+  return SB_OK;
+}
+
+uint64_t sb_select_num_rows(const sb_select* s) { return s ? s->n_selected : 0; }
+uint64_t sb_select_num_pages(const sb_select* s) { return s ? s->touched.size() : 0; }
+
+sb_status sb_select_page(const sb_select* s, uint64_t i, uint64_t* page_index, uint64_t* selected) {
+  if (!s || i >= s->touched.size()) return SB_E_ARG;
+  if (page_index) *page_index = s->touched[i];
+  if (selected) *selected = s->counts[s->touched[i]];
+  return SB_OK;
+}
+
+void sb_select_destroy(sb_select* s) { delete s; }
+
+sb_status sb_plan_selected_column(sb_ctx* ctx, const sb_column_desc* desc, const sb_select* sel,
+                                  const uint8_t* d_chunk, uint64_t chunk_len, int32_t packed, sb_plan** out) {
+  if (!ctx || !desc || !sel || !out) return SB_E_ARG;
+  if (!d_chunk && !sel->touched.empty()) return fail(ctx, SB_E_ARG, "null column chunk");
+  bool is_float;
+  const int ptype = desc->physical_type;
+  const int width = type_width(ptype, &is_float);
+  const int owidth = (ptype == SB_T_BINARY || ptype == SB_T_UTF8) ? 4
+                     : (ptype == SB_T_LARGE_BINARY || ptype == SB_T_LARGE_UTF8) ? 8 : 0;
+  const bool is_bool = ptype == SB_T_BOOLEAN;
+  if (!width && !owidth && !is_bool) return fail(ctx, SB_E_NYI, "physical type %d not supported", ptype);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+  SelState* s = new SelState();
+  sb_plan* p = new sb_plan();
+  p->sel = s;
+  p->desc = *desc;
+  p->d_chunk = d_chunk;
+  p->chunk_len = chunk_len;
+  p->width = width;
+  p->is_float = is_float;
+  p->binary = owidth != 0;
+  p->boolean = is_bool;
+  p->offset_width = owidth;
+  p->n_rows = sel->n_selected;
+  p->n_pages = sel->touched.size();
+  s->d_sel = (const uint32_t*)sel->d_selection;
+
+  // The page tables: both chunk layouts differ only in byte_off.
+  std::vector<sb::PageDesc> direct, part;
+  std::vector<sb::SelPage> sp;
+  std::vector<uint32_t> tiles;
+  uint64_t col_off = 0, packed_off = 0, col_row = 0, out_row = 0;
+  for (size_t i = 0; i < sel->metas.size(); i++) {
+    const sb_page_meta& m = sel->metas[i];
+    const uint64_t cnt = sel->counts[i];
+    if (cnt) {
+      const uint64_t boff = packed ? packed_off : col_off;
+      if (!owidth && cnt == m.num_values) {
+        direct.push_back(sb::PageDesc{boff, out_row, (uint32_t)m.length, (uint32_t)m.num_values, 0});
+        s->direct_ids.push_back((uint32_t)i);
+      } else {
+        part.push_back(sb::PageDesc{boff, s->part_rows, (uint32_t)m.length, (uint32_t)m.num_values, 0});
+        s->part_ids.push_back((uint32_t)i);
+        const uint32_t nt = (uint32_t)((m.num_values + sb::kSelTileRows - 1) / sb::kSelTileRows);
+        for (uint32_t t = 0; t < nt; t++) {
+          tiles.push_back((uint32_t)sp.size());
+          tiles.push_back(t);
+        }
+        sp.push_back(sb::SelPage{col_row, s->part_rows, out_row, (uint32_t)m.num_values, 0});
+        // (a binary scratch column is dense; fixed-width pages start on a validity word)
+        s->part_rows += owidth ? m.num_values : (m.num_values + 31) & ~31ull;
+      }
+      packed_off += m.length;
+      out_row += cnt;
+    }
+    col_off += m.length;
+    col_row += m.num_values;
+  }
+  if (tiles.size() / 2 > 0x7FFFFFFFull) {
+    sb_plan_destroy(p);
+    return fail(ctx, SB_E_ARG, "too many pages");
+  }
+  s->n_tiles = (uint32_t)(tiles.size() / 2);
+
+  sb_status st = SB_OK;
+  if (!direct.empty())
+    st = plan_pages(ctx, desc, d_chunk, chunk_len, std::move(direct), &s->direct, kRegionsProbe, s->direct_ids.data());
+  if (!st && !part.empty())
+    st = plan_pages(ctx, desc, d_chunk, chunk_len, std::move(part), &s->part, kRegionsProbe, s->part_ids.data());
+  if (st) {
+    sb_plan_destroy(p);
+    return st;
+  }
+  if (s->part) {
+    p->values_bytes = s->part->values_bytes;
+    // scratch: [SelPage table | tile list | tile bases (binary) | values | validity | offsets (binary)]
+    const uint64_t words = 4 * ((s->part_rows + 31) / 32);
+    const uint64_t b_sp = sb::align16(sp.size() * sizeof(sb::SelPage));
+    const uint64_t b_tiles = sb::align16(tiles.size() * sizeof(uint32_t));
+    const uint64_t b_tb = owidth ? sb::align16((s->n_tiles + 1ull) * sizeof(uint64_t)) : 0;
+    s->s_values_len = owidth ? s->part->values_bytes : is_bool ? words : s->part_rows * (uint64_t)width;
+    const uint64_t b_values = sb::align16(s->s_values_len) + 16;
+    const uint64_t b_valid = desc->nullable ? sb::align16(words) + 16 : 0;
+    const uint64_t b_aux = owidth ? sb::align16((s->part_rows + 1) * (uint64_t)owidth) : 0;
+    s->scratch_bytes = b_sp + b_tiles + b_tb + b_values + b_valid + b_aux;
+    hipError_t e = hipMalloc(&s->d_scratch, s->scratch_bytes);
+    if (e == hipSuccess) {
+      uint8_t* q = s->d_scratch;
+      s->d_sp = (sb::SelPage*)q, q += b_sp;
+      s->d_tiles = (uint32_t*)q, q += b_tiles;
+      if (owidth) s->d_tile_bytes = (uint64_t*)q, q += b_tb;
+      s->s_values = q, q += b_values;
+      if (desc->nullable) s->s_validity = q, q += b_valid;
+      if (owidth) s->s_aux = q;
+      e = hipMemcpyAsync(s->d_sp, sp.data(), sp.size() * sizeof(sb::SelPage), hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(s->d_tiles, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // host vectors go out of scope
+    if (e != hipSuccess) {
+      sb_plan_destroy(p);
+      return fail(ctx, SB_E_DEVICE, "selective plan scratch: %s", hipGetErrorString(e));
+    }
+  }
+  *out = p;
+  return SB_OK;
+}
+
+sb_status sb_decode_selected(sb_ctx* ctx, sb_plan* p, const sb_primitive_out* out) {
+  if (!ctx || !p || !out) return SB_E_ARG;
+  if (!p->sel) return fail(ctx, SB_E_ARG, "not a selective plan");
+  if (p->binary) return fail(ctx, SB_E_ARG, "binary plan: use sb_decode_binary_selected");
+  if (!p->n_rows) return SB_OK;  // no row selected: no page, no launch
+  if (!out->d_values) return fail(ctx, SB_E_ARG, "values buffer is null");
+  if (p->desc.nullable && !out->d_validity) return fail(ctx, SB_E_ARG, "validity buffer is null");
+  SelState* s = p->sel;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t words = (p->n_rows + 31) / 32 * 4;
+  if (s->part) {  // the take pass ORs its edge words; the direct pages then only add theirs
+    if (p->desc.nullable) HIP_TRY(ctx, hipMemsetAsync(out->d_validity, 0, words, ctx->stream));
+    if (p->boolean) HIP_TRY(ctx, hipMemsetAsync(out->d_values, 0, words, ctx->stream));
+  }
+  if (s->direct) {
+    const sb_status st = sb_decode_planned(ctx, s->direct, out);
+    if (st) return st;
+  }
+  if (s->part) {
+    const sb_primitive_out so{s->s_values, s->s_validity};
+    const sb_status st = sb_decode_planned(ctx, s->part, &so);
+    if (st) return st;
+    sb::SelTake t{};
+    t.sel = s->d_sel;
+    t.pages = s->d_sp;
+    t.tiles = s->d_tiles;
+    t.n_tiles = s->n_tiles;
+    if (p->boolean) {
+      t.src_bits[1] = (const uint32_t*)s->s_values;
+      t.dst_bits[1] = (uint32_t*)out->d_values;
+    } else {
+      t.src_values = s->s_values;
+      t.dst_values = (uint8_t*)out->d_values;
+    }
+    if (p->desc.nullable) {
+      t.src_bits[0] = (const uint32_t*)s->s_validity;
+      t.dst_bits[0] = (uint32_t*)out->d_validity;
+    }
+    if (sb::launch_sel_take(p->boolean ? 0 : p->width, t, ctx->stream))
+      return fail(ctx, SB_E_DEVICE, "take launch failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  return SB_OK;
+}
+
+sb_status sb_decode_binary_selected(sb_ctx* ctx, sb_plan* p, const sb_binary_out* out) {
+  if (!ctx || !p || !out) return SB_E_ARG;
+  if (!p->sel) return fail(ctx, SB_E_ARG, "not a selective plan");
+  if (!p->binary) return fail(ctx, SB_E_ARG, "not a binary plan");
+  if (!out->d_offsets) return fail(ctx, SB_E_ARG, "offsets buffer is null");
+  if ((uintptr_t)out->d_offsets % p->offset_width) return fail(ctx, SB_E_ARG, "offsets buffer is not aligned");
+  SelState* s = p->sel;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!s->part) {  // no row selected: offsets [0]
+    HIP_TRY(ctx, hipMemsetAsync(out->d_offsets, 0, (size_t)p->offset_width, ctx->stream));
+    return SB_OK;
+  }
+  if (p->values_bytes && (!out->d_values || out->values_capacity < p->values_bytes))
+    return fail(ctx, SB_E_ARG, "binary output buffers too small");
+  if (p->desc.nullable && !out->d_validity) return fail(ctx, SB_E_ARG, "validity buffer is null");
+  if (p->desc.nullable) HIP_TRY(ctx, hipMemsetAsync(out->d_validity, 0, (p->n_rows + 31) / 32 * 4, ctx->stream));
+  const sb_binary_out so{s->s_aux, s->s_values, sb::align16(s->s_values_len) + 16, s->s_validity};
+  const sb_status st = sb_decode_binary_planned(ctx, s->part, &so);
+  if (st) return st;
+  sb::SelBin b{};
+  b.sel = s->d_sel;
+  b.pages = s->d_sp;
+  b.tiles = s->d_tiles;
+  b.n_tiles = s->n_tiles;
+  b.src_offsets = s->s_aux;
+  b.src_values = s->s_values;
+  b.src_len = s->s_values_len;
+  b.src_validity = p->desc.nullable ? (const uint32_t*)s->s_validity : nullptr;
+  b.dst_offsets = (uint8_t*)out->d_offsets;
+  b.dst_values = out->d_values;
+  b.values_cap = out->values_capacity;
+  b.dst_validity = (uint32_t*)out->d_validity;
+  b.tile_bytes = s->d_tile_bytes;
+  if (sb::launch_sel_take_bin(p->offset_width, b, ctx->stream))
+    return fail(ctx, SB_E_DEVICE, "binary take launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return SB_OK;
+}
+
+sb_status sb_plan_selected_values_bytes(sb_ctx* ctx, sb_plan* p, uint64_t* bytes) {
+  if (!ctx || !p || !bytes) return SB_E_ARG;
+  if (!p->sel) return fail(ctx, SB_E_ARG, "not a selective plan");
+  *bytes = 0;
+  if (!p->binary) {
+    *bytes = p->boolean ? (p->n_rows + 31) / 32 * 4 : p->n_rows * (uint64_t)p->width;
+    return SB_OK;
+  }
+  if (!p->sel->part) return SB_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipMemcpyAsync(bytes, p->sel->d_tile_bytes + p->sel->n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost,
+                              ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return SB_OK;
+}
+
+sb_status sb_plan_selected_stats(const sb_plan* p, uint64_t* pages_direct, uint64_t* pages_compacted,
+                                 uint64_t* scratch_bytes) {
+  if (!p || !p->sel) return SB_E_ARG;
+  if (pages_direct) *pages_direct = p->sel->direct_ids.size();
+  if (pages_compacted) *pages_compacted = p->sel->part_ids.size();
+  if (scratch_bytes) *scratch_bytes = p->sel->scratch_bytes;
   return SB_OK;
 }
 

@@ -288,4 +288,49 @@ struct NestLaunch {
 };
 int launch_nest(int stage, const NestLaunch& a, void* stream);
 
+// Selective reads (sb_select.hip): a selection is an LSB-first bitmap over a
+// flat column's rows.  A compacted page: its rows [sel_row, + num_values) of
+// the column (its selection bits), decoded at rows src_row.. of the plan's
+// scratch, its selected rows appended at dst_row of the output.
+struct SelPage {
+  uint64_t sel_row;
+  uint64_t src_row;
+  uint64_t dst_row;
+  uint32_t num_values;
+  uint32_t reserved;
+};
+static_assert(sizeof(SelPage) == 32, "selected page entry is 32 bytes");
+constexpr uint32_t kSelTileRows = 4096;  // rows of a page one take workgroup compacts
+// counts[p] = set selection bits in rows [row_offs[p], row_offs[p + 1]).
+int launch_sel_count(const uint32_t* sel, const uint64_t* row_offs, uint32_t n_pages, uint64_t* counts, void* stream);
+struct SelTake {
+  const uint32_t* sel;
+  const SelPage* pages;
+  const uint32_t* tiles;  // [2 n_tiles]: (page, tile of the page) of each workgroup
+  uint32_t n_tiles;
+  const uint8_t* src_values;
+  uint8_t* dst_values;
+  const uint32_t* src_bits[2];  // [0] validity, [1] a Boolean column's values bitmap; nullptr = none
+  uint32_t* dst_bits[2];        // zeroed by the host: edge words are ORed
+};
+// width: 1 / 2 / 4 / 8, or 0 = bitmaps only (Boolean).
+int launch_sel_take(int width, const SelTake& a, void* stream);
+struct SelBin {
+  const uint32_t* sel;
+  const SelPage* pages;
+  const uint32_t* tiles;
+  uint32_t n_tiles;
+  const uint8_t* src_offsets;    // the scratch column: rows + 1 offsets
+  const uint8_t* src_values;
+  uint64_t src_len;              // its values bytes
+  const uint32_t* src_validity;  // or nullptr
+  uint8_t* dst_offsets;
+  uint8_t* dst_values;
+  uint64_t values_cap;
+  uint32_t* dst_validity;        // zeroed by the host
+  uint64_t* tile_bytes;          // [n_tiles + 1]: each tile's values base, then the total
+};
+// Sizing pass, scan and take pass of a Binary / Utf8 column (three launches).
+int launch_sel_take_bin(int offset_width, const SelBin& a, void* stream);
+
 }  // namespace sb

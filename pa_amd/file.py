@@ -85,6 +85,7 @@ class StrawboatFile:
         L = N.lib()
         self.num_columns = int(L.sb_file_num_columns(self._h))
         self._columns: Optional[List[ColumnMeta]] = None
+        self.last_uploaded_bytes = 0  # bytes the last read_selected moved to the device
         b, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
         self._check(L.sb_file_schema(self._h, ctypes.byref(b), ctypes.byref(n)))
         self.schema_bytes = ctypes.string_at(b, n.value)
@@ -214,6 +215,16 @@ class StrawboatFile:
             return dec.decode()
         finally:
             dec.close()
+
+    def read_selected(self, col: int, selection, ctx: Optional[Context] = None):
+        """The rows of flat leaf column `col` that `selection`
+        (pa_amd.Selection) names: only the runs of touched pages are uploaded
+        (their bytes: last_uploaded_bytes) and decoded.  Fixed width /
+        Boolean -> (values, validity), Binary / Utf8 -> (offsets, values,
+        validity).  A nested leaf raises StrawboatError(E_NYI)."""
+        from .select import file_read_selected
+
+        return file_read_selected(self, col, selection, ctx)
 
     def close(self):
         if getattr(self, "_h", None):

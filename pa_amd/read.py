@@ -241,6 +241,17 @@ class ColumnDecoder:
         dec.shard = shard
         return dec
 
+    @classmethod
+    def select(cls, chunk, page_metas, dtype, nullable: bool, selection, ctx=None, packed: bool = False):
+        """The decoder of the rows `selection` (pa_amd.Selection) names: pages
+        without a selected row are not planned or decoded, and with
+        packed=True `chunk` holds only the touched pages, back to back
+        (pa_amd.page_runs).  Same alloc_outputs / decode_async / check /
+        decode / close; the outputs hold the selected rows only."""
+        from .select import SelectedColumnDecoder
+
+        return SelectedColumnDecoder(chunk, page_metas, dtype, nullable, selection, ctx, packed)
+
     def alloc_outputs(self):
         torch = self._torch
         dev = f"cuda:{self.ctx.device}"

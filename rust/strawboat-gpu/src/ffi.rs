@@ -7,6 +7,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct sb_ctx { _p: [u8; 0] }
 #[repr(C)] pub struct sb_plan { _p: [u8; 0] }
 #[repr(C)] pub struct sb_file { _p: [u8; 0] }
+#[repr(C)] pub struct sb_select { _p: [u8; 0] }
 
 pub const SB_MAX_NEST: usize = 4;
 
@@ -74,6 +75,19 @@ extern "C" {
     pub fn sb_plan_column_at(ctx: *mut sb_ctx, desc: *const sb_column_desc, d_chunk: *const u8, chunk_len: u64,
                              metas: *const sb_page_meta, n_pages: u64, row_offsets: *const u64,
                              out: *mut *mut sb_plan) -> i32;
+    pub fn sb_select_create(ctx: *mut sb_ctx, d_selection: *const u8, n_rows: u64, metas: *const sb_page_meta,
+                            n_pages: u64, out: *mut *mut sb_select) -> i32;
+    pub fn sb_select_num_rows(sel: *const sb_select) -> u64;
+    pub fn sb_select_num_pages(sel: *const sb_select) -> u64;
+    pub fn sb_select_page(sel: *const sb_select, i: u64, page_index: *mut u64, selected: *mut u64) -> i32;
+    pub fn sb_select_destroy(sel: *mut sb_select);
+    pub fn sb_plan_selected_column(ctx: *mut sb_ctx, desc: *const sb_column_desc, sel: *const sb_select,
+                                   d_chunk: *const u8, chunk_len: u64, packed: i32, out: *mut *mut sb_plan) -> i32;
+    pub fn sb_decode_selected(ctx: *mut sb_ctx, plan: *mut sb_plan, out: *const sb_primitive_out) -> i32;
+    pub fn sb_decode_binary_selected(ctx: *mut sb_ctx, plan: *mut sb_plan, out: *const sb_binary_out) -> i32;
+    pub fn sb_plan_selected_values_bytes(ctx: *mut sb_ctx, plan: *mut sb_plan, bytes: *mut u64) -> i32;
+    pub fn sb_plan_selected_stats(plan: *const sb_plan, pages_direct: *mut u64, pages_compacted: *mut u64,
+                                  scratch_bytes: *mut u64) -> i32;
     pub fn sb_plan_destroy(plan: *mut sb_plan);
     pub fn sb_plan_num_rows(plan: *const sb_plan) -> u64;
     pub fn sb_plan_values_bytes(plan: *const sb_plan) -> u64;
