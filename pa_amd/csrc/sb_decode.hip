@@ -775,11 +775,8 @@ typedef __attribute__((address_space(3))) uint8_t lds_u8;
 #ifndef SB_INF_FAR128
 #define SB_INF_FAR128 1  // free matches' far sources: one 16-byte load for their first four dwords
 #endif
-#ifdef SB_INF_RING4K  // (before round 6) 4 KiB rings, 1 KiB chunks: 6.5 KiB of LDS a wave, six waves a SIMD
-constexpr uint32_t kRing = 4096, kChunk = 1024;
-#else  // 2 KiB rings, 512-byte chunks: 4.5 KiB of LDS a wave, eight waves a SIMD
+// 2 KiB rings, 512-byte chunks: 4.5 KiB of LDS a wave, eight waves a SIMD
 constexpr uint32_t kRing = 2048, kChunk = 512;
-#endif
 constexpr uint32_t kInfWaves = SB_INF_WPB;  // waves (jobs in flight) per k_inflate workgroup
 
 // Far-history reads re-read bytes this wave stored and waited for (vmcnt(0))
@@ -1534,10 +1531,8 @@ __device__ uint32_t lz4_inflate(InRing& in, uint32_t p, uint32_t pend, WaveOut<t
   uint64_t tph = __builtin_amdgcn_s_memtime();
   INF_N(13, 1);
 #endif
-  // the chain of the batch at p: found at the loop's top, or (SB_INF_PIPE)
-  // by the previous batch while its far loads were in flight
+  // the chain of the batch at p
   uint32_t cx = 0, j = 0;
-  bool have = false;
   // 1. successor distances of the candidate starts x = p + 4 lane + k, from
   //    the token and at most one extension byte per length: the tokens are
   //    one unaligned dword of the ring, the literal extensions the next
@@ -1548,17 +1543,11 @@ __device__ uint32_t lz4_inflate(InRing& in, uint32_t p, uint32_t pend, WaveOut<t
     in.slide(q);
     const uint32_t lim = min(in.base + kIb, pend);
     const uint32_t t1 = cand_steps(in.ib, q, lim, pend);
-#ifdef SB_INF_BPCHAIN  // the chain by ds_bpermute doubling: no LDS tables
-    cx = wave_chain(t1);
-    j = (uint32_t)__popcll(__ballot(cx < kChainEnd && tab_at(t1, cx) != kChainStop));
-#else
     cx = lds_chain(in.ct, t1);
     j = (uint32_t)__popcll(__ballot(cx < kChainEnd && in.ct[cx] != kChainStop));
-#endif
   };
   while (p < pend && !ended) {
-    if (!have) chain_at(p);
-    have = false;
+    chain_at(p);
     INF_T(2);
     const uint32_t starts = p + cx;
     // 3. decode and place
@@ -1596,26 +1585,6 @@ __device__ uint32_t lz4_inflate(InRing& in, uint32_t p, uint32_t pend, WaveOut<t
 #ifdef SB_V_NOLIT
     if (v) s.lit = 0;
 #endif
-#ifdef SB_INF_EARLYFAR
-    // The free matches' sources are final before the batch (below d_first), and
-    // those below farlim are in HBM: their first dwords are loaded now, so the
-    // loads' latency passes under the literal copies.
-    const uint32_t d_first = __builtin_amdgcn_readfirstlane(dm);
-    const uint32_t src = dm - s.off;
-    const bool hazard = v && (src + s.ml > d_first || s.ml > kMatchFast);
-    const bool freel = v && !hazard;
-    const uint32_t farlim = o.far_limit();
-    const bool mfar = src + s.ml <= farlim, mnear = src >= farlim;
-    const bool fw = freel && (mfar || mnear);
-    const uint32_t fa = mfar ? src + o.dal : src, fsh = fa & 3, fa0 = fa - fsh, fneed = fw ? fsh + s.ml : 0u;
-    constexpr uint32_t kEarly = 3;
-    uint32_t pw[kEarly];
-#pragma unroll
-    for (uint32_t t = 0; t < kEarly; t++) {
-      const bool need = fw && mfar && 4 * t < fneed;
-      pw[t] = __ballot(need) ? o.far32(fa0 + 4 * t, need) : 0u;
-    }
-#endif
     // literals, 16 bytes per lane per step: source dwords from the input ring,
     // one masked dword store per destination word
     for (uint32_t c = 0; __ballot(v && c < s.lit); c += 16) {
@@ -1627,16 +1596,7 @@ __device__ uint32_t lz4_inflate(InRing& in, uint32_t p, uint32_t pend, WaveOut<t
         ring_put<5>(o.ring, dl + c, n, sh, w);
       }
     }
-#ifdef SB_INF_PIPE
-    // the next batch's candidates and chain, under the far loads' latency (the
-    // literals are in the output ring: the input ring may slide)
-    if (pnext < pend) {
-      chain_at(pnext);
-      have = true;
-    }
-#endif
     INF_T(4);
-#ifndef SB_INF_EARLYFAR
     const uint32_t d_first = __builtin_amdgcn_readfirstlane(dm);
     const uint32_t src = dm - s.off;
 #ifdef SB_V_NOHAZ
@@ -1657,11 +1617,10 @@ __device__ uint32_t lz4_inflate(InRing& in, uint32_t p, uint32_t pend, WaveOut<t
     const bool mfar = src + s.ml <= farlim, mnear = src >= farlim;
     const bool fw = freel && (mfar || mnear);
     const uint32_t fa = mfar ? src + o.dal : src, fsh = fa & 3, fa0 = fa - fsh, fneed = fw ? fsh + s.ml : 0u;
-#endif
     if (__ballot(fw)) {
       constexpr uint32_t NW = kMatchFast / 4 + 1;
       uint32_t w[NW];
-#if SB_INF_FAR128 && !defined(SB_INF_EARLYFAR)
+#if SB_INF_FAR128
       // the far source's first 16 bytes in one load (C3 3.81 -> 3.65 ms a
       // step: one vector-memory instruction instead of up to four)
       const bool f4 = fw && mfar;
@@ -1671,19 +1630,7 @@ __device__ uint32_t lz4_inflate(InRing& in, uint32_t p, uint32_t pend, WaveOut<t
       for (uint32_t t = 0; t < NW; t++) {
         w[t] = 0;
         if (!__ballot(4 * t < fneed)) continue;
-#ifdef SB_INF_EARLYFAR
-        // ring sources now (this batch's literals are in); far dwords past the
-        // early ones loaded here, only when some lane needs them
-        const bool nr = !mfar && 4 * t < fneed;
-        const uint32_t r = __ballot(nr) ? r32[((fa0 + 4 * t) & (kRing - 1)) >> 2] : 0u;
-        uint32_t g;
-        if (t < kEarly) {
-          g = pw[t < kEarly ? t : 0];
-        } else {
-          const bool nf = mfar && 4 * t < fneed;
-          g = __ballot(nf) ? o.far32(fa0 + 4 * t, nf) : 0u;
-        }
-#elif SB_INF_FAR128
+#if SB_INF_FAR128
         const uint32_t g = t < 4 ? g4[t < 4 ? t : 0] : o.far32(fa0 + 4 * t, mfar && 4 * t < fneed);
         const uint32_t r = r32[((fa0 + 4 * t) & (kRing - 1)) >> 2];
 #else
@@ -1708,44 +1655,6 @@ __device__ uint32_t lz4_inflate(InRing& in, uint32_t p, uint32_t pend, WaveOut<t
     // the ring, <= 64 bytes) is one byte a lane; its ring positions and
     // length are packed per lane beforehand, so each takes one v_readlane.
     const bool hfast = hazard && s.ml <= 64 && s.off >= s.ml && src >= farlim;
-#ifdef SB_INF_HAZGROUP
-    // Consecutive fast hazards go as one group, one byte a lane: a member joins
-    // while the group's bytes fit the wave and its source lies outside the
-    // span of the group's destinations (every earlier byte it reads is then
-    // final), so a group costs one LDS read and one store instead of a pair
-    // per hazard.  Positions are packed relative to op - kRing (13 bits each:
-    // sources reach back at most the ring, destinations a chunk ahead).
-    const uint32_t rel0 = o.op - kRing;
-    const uint32_t hpack = hfast ? ((src - rel0) << 19) | ((dm - rel0) << 6) | (s.ml - 1) : 0u;
-    const uint64_t fastm = __ballot(hfast);
-    for (uint64_t hm = __ballot(hazard); hm;) {
-      const uint32_t l = (uint32_t)__builtin_ctzll(hm);
-      if ((fastm >> l) & 1) {
-        uint32_t base = 0, gd0 = 0, gend = 0, rs = 0, rd = 0;
-        bool act = false;
-        while (hm && ((fastm >> __builtin_ctzll(hm)) & 1)) {
-          const uint32_t h = __builtin_amdgcn_readlane(hpack, (uint32_t)__builtin_ctzll(hm));
-          const uint32_t m = (h & 63u) + 1u, hs = h >> 19, hd = (h >> 6) & 0x1FFFu;
-          if (base) {
-            if (base + m > 64u || !(hs + m <= gd0 || hs >= gend)) break;
-          } else {
-            gd0 = hd;
-          }
-          if (lane >= base && lane < base + m) {
-            rs = hs + lane - base;
-            rd = hd + lane - base;
-            act = true;
-          }
-          base += m;
-          gend = hd + m;
-          hm &= hm - 1;
-        }
-        const uint32_t b = act ? (uint32_t)o.ring[(rs + rel0) & (kRing - 1)] : 0u;
-        if (act) o.ring[(rd + rel0) & (kRing - 1)] = (uint8_t)b;
-        continue;
-      }
-      hm &= hm - 1;
-#else
     const uint32_t hpack = ((src & (kRing - 1)) << 20) | ((dm & (kRing - 1)) << 8) | (hfast ? s.ml : 0u);
     const uint64_t fastm = __ballot(hfast);
     for (uint64_t hm = __ballot(hazard); hm; hm &= hm - 1) {
@@ -1756,7 +1665,6 @@ __device__ uint32_t lz4_inflate(InRing& in, uint32_t p, uint32_t pend, WaveOut<t
           o.ring[((h >> 8) + lane) & (kRing - 1)] = o.ring[((h >> 20) + lane) & (kRing - 1)];
         continue;
       }
-#endif
       const uint32_t D = __builtin_amdgcn_readlane(dm, l), O = __builtin_amdgcn_readlane(s.off, l),
                      M = __builtin_amdgcn_readlane(s.ml, l);
       for (uint32_t c = 0; c < M; c += 64) {
@@ -2655,20 +2563,12 @@ static int launch(int kind, const LaunchArgs& a, hipStream_t stream) {
 // workgroup, so 8 waves per SIMD can be resident and the serial token streams
 // of many pages overlap.
 #ifndef SB_INF_BLOCKS
-#ifdef SB_INF_RING4K
-#define SB_INF_BLOCKS 6  // 4-wave workgroups: 6 waves per SIMD (6.5 KiB of LDS and <= 80 VGPRs a wave)
-#else
 #define SB_INF_BLOCKS 8  // 4-wave workgroups: 8 waves per SIMD (4.5 KiB of LDS and <= 64 VGPRs a wave)
-#endif
 #endif
 __global__ __launch_bounds__(64 * kInfWaves, SB_INF_BLOCKS) void k_inflate(InflateLaunch a) {
   __shared__ u32x4 rings[kInfWaves][kRing / 16];
   __shared__ u32x4 ibufs[kInfWaves][kIb / 16];
-#ifdef SB_INF_BPCHAIN
-  u32x4* const ctabs[kInfWaves] = {};
-#else
   __shared__ u32x4 ctabs[kInfWaves][kChainTabs * 256 / 16];
-#endif
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t n = a.count ? *a.count : a.n_jobs;

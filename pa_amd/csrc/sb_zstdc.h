@@ -15,10 +15,12 @@
 //     kZSeqPerBlock sequences: the block's literals (zstd_literals: a
 //     Huffman-coded 4-stream Compressed_Literals_Block with a directly
 //     represented table when that is smaller, an RLE block for one repeated
-//     byte, else Raw), then the sequences under the Predefined_Mode FSE
-//     tables of literal lengths, match lengths and offsets (RFC 8878
-//     §3.1.1.3.2.2), every offset a new one (Offset_Value = offset + 3, no
-//     repeat codes), encoded last sequence first as libzstd's
+//     byte, else Raw), then the sequences, each of the literal-length,
+//     match-length and offset tables in the cheapest of Predefined_Mode,
+//     RLE_Mode and FSE_Compressed_Mode with the block's own table (RFC 8878
+//     §3.1.1.3.2.2, seq_table); an offset equal to one of the frame's repeat
+//     offsets takes its repeat code (§3.1.2.5, ZRep), any other is
+//     Offset_Value = offset + 3; encoded last sequence first as libzstd's
 //     ZSTD_encodeSequences does; a block that would not shrink is written
 //     Raw instead.
 // Decode equivalence is checked against libzstd by tests/test_zstdc.py
