@@ -1051,6 +1051,30 @@ struct WaveOut {
   }
 };
 
+// The end-of-block rules as LZ4_decompress_safe holds a block to them (the
+// reference returns its error, basic.rs:87-91).  A sequence whose literals
+// end within the last 12 output bytes, or with fewer than 8 input bytes
+// behind them, must be the last: literals only, to the end of both buffers.
+// A match must end at least 5 bytes before the end of the output.
+// One exception is the library's own: its two-stage shortcut copies a
+// sequence that starts at least 32 bytes before the end of the output, with
+// more than 16 input bytes behind its token and a literal length below 15,
+// without the literal checks -- and, when the match length is below 19 and
+// the offset at least 8, without the match check either.
+// p: the position behind the token.
+__device__ __forceinline__ bool lz4_shortcut(uint32_t token, uint32_t p, uint32_t pend, uint32_t op, uint32_t olen) {
+  return (token >> 4) != 15 && pend - p > 16 && olen - op >= 32;
+}
+// lit <= pend - p, lit <= olen - op: the literals end the block
+__device__ __forceinline__ bool lz4_last(bool sc, uint32_t lit, uint32_t p, uint32_t pend, uint32_t op, uint32_t olen) {
+  return !sc && (olen - op - lit < 12 || pend - p - lit < 8);
+}
+// ml <= olen - op (op: behind the literals): the match may end there
+__device__ __forceinline__ bool lz4_match_ends_ok(bool sc, uint32_t token, uint32_t off, uint32_t ml, uint32_t op,
+                                                  uint32_t olen) {
+  return olen - op - ml >= 5 || (sc && (token & 15) != 15 && off >= 8);
+}
+
 template <bool RING>
 __device__ uint32_t lz4_wave(WaveWin& w, uint32_t p, uint32_t pend, WaveOut<RING>& o) {
   const uint32_t olen = o.olen;
@@ -1058,6 +1082,7 @@ __device__ uint32_t lz4_wave(WaveWin& w, uint32_t p, uint32_t pend, WaveOut<RING
   for (;;) {
     w.slide(p);
     const uint32_t token = w.byte(p++);
+    const bool sc = lz4_shortcut(token, p, pend, o.op, olen);
     uint32_t lit = token >> 4;
     if (lit == 15) {
       uint32_t b;
@@ -1068,6 +1093,8 @@ __device__ uint32_t lz4_wave(WaveWin& w, uint32_t p, uint32_t pend, WaveOut<RING
       } while (b == 255);
     }
     if (lit > pend - p || lit > olen - o.op) return ST_CODEC;
+    const bool last = lz4_last(sc, lit, p, pend, o.op, olen);
+    if (last && (lit != pend - p || lit != olen - o.op)) return ST_CODEC;
     while (lit) {
       w.slide(p);
       const uint32_t m = min(lit, o.room());
@@ -1075,7 +1102,7 @@ __device__ uint32_t lz4_wave(WaveWin& w, uint32_t p, uint32_t pend, WaveOut<RING
       p += m;
       lit -= m;
     }
-    if (p == pend) break;  // the last sequence carries literals only
+    if (last) break;  // the last sequence carries literals only
     if (pend - p < 2) return ST_CODEC;
     w.slide(p);
     const uint32_t off = w.byte(p) | (w.byte(p + 1) << 8);
@@ -1090,12 +1117,13 @@ __device__ uint32_t lz4_wave(WaveWin& w, uint32_t p, uint32_t pend, WaveOut<RING
         ml += b;
       } while (b == 255);
     }
-    if (ml > olen - o.op) return ST_CODEC;
+    if (ml > olen - o.op || !lz4_match_ends_ok(sc, token, off, ml, o.op, olen)) return ST_CODEC;
     while (ml) {
       const uint32_t m = min(ml, o.room());
       o.match(off, m);
       ml -= m;
     }
+    if (p >= pend) return ST_CODEC;  // (no token behind the match)
   }
   if (o.op != olen) return ST_CODEC;
   o.finish();
@@ -1174,8 +1202,9 @@ __device__ uint32_t snappy_wave(WaveWin& w, uint32_t p, uint32_t pend, WaveOut<R
 // compressed bytes, so the walk is restated data-parallel per batch:
 //  1. every lane parses a sequence at 4 candidate positions p + 4 lane + k
 //     (k < 4) and packs the byte distance to its successor (0 = take the
-//     serial path: final literal-only sequence, literal > kLitFast, lengths
-//     past the staged input, a distance > 255);
+//     serial path: final literal-only sequence, literals with fewer than 8
+//     input bytes behind them, literal > kLitFast, lengths past the staged
+//     input, a distance > 255);
 //  2. a scalar chase follows successors from p (one v_readlane per sequence)
 //     and deals the true sequence starts to lanes;
 //  3. lanes decode their sequence, a wave scan places the outputs (at most a
@@ -1402,7 +1431,9 @@ __device__ __forceinline__ uint32_t cand_steps(const lds_u8* ib, uint32_t p, uin
   const uint32_t nxt = __builtin_amdgcn_alignbyte(w2, w1, sh);   // bytes x0 + 4 .. x0 + 7
   const uint32_t ext = __builtin_amdgcn_alignbyte(nxt, tok, 1);  // bytes x0 + 1 .. x0 + 4
   uint32_t t1 = 0;
-  if (lim - p >= 261 + kLitFast) {  // every candidate's bytes (<= p + 260 + kLitFast) are staged: no bounds checks
+  // every candidate's bytes (<= p + 260 + kLitFast) are staged, and its literals
+  // end at least 8 bytes before lim <= pend (the input-side end rule): no bounds checks
+  if (lim - p >= 269 + kLitFast) {
 #pragma unroll
     for (uint32_t k = 0; k < 4; k++) {
       const uint32_t x = x0 + k, t = (tok >> (8 * k)) & 0xFFu, e = (ext >> (8 * k)) & 0xFFu;
@@ -1423,7 +1454,8 @@ __device__ __forceinline__ uint32_t cand_steps(const lds_u8* ib, uint32_t p, uin
     const bool lx = ln == 15;
     const uint32_t lit = lx ? 15 + e : ln;
     const uint32_t le = x + 1 + (uint32_t)lx + lit;  // the offset's position
-    bool ok = x + 1 + (uint32_t)lx <= lim && lit <= kLitFast && le + 2 <= lim && le < pend;
+    // (le + 8 <= pend: 8 input bytes behind a non-final sequence's literals)
+    bool ok = x + 1 + (uint32_t)lx <= lim && lit <= kLitFast && le + 2 <= lim && le + 8 <= pend;
     uint32_t y = le + 2;
     if (ok && (t & 15) == 15) {
       const uint32_t e2 = y < lim ? (uint32_t)ib[y & (kIb - 1)] : 255u;
@@ -1460,11 +1492,14 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {  // DPP: no LDS
   return v;
 }
 
-// One sequence at *pp, serially (the liblz4 checks of lz4_wave).
+// One sequence at *pp, serially, with every check of lz4_wave: the bounds and
+// liblz4's end-of-block rules (lz4_shortcut).  The batch path leaves every
+// sequence near either end of the block to this one.
 __device__ uint32_t lz4_one(InRing& in, uint32_t* pp, uint32_t pend, WaveOut<true>& o, bool* ended) {
   uint32_t p = *pp;
   const uint32_t olen = o.olen;
   const uint32_t token = in.ubyte(p++);
+  const bool sc = lz4_shortcut(token, p, pend, o.op, olen);
   uint32_t lit = token >> 4;
   if (lit == 15) {
     uint32_t b;
@@ -1475,9 +1510,11 @@ __device__ uint32_t lz4_one(InRing& in, uint32_t* pp, uint32_t pend, WaveOut<tru
     } while (b == 255);
   }
   if (lit > pend - p || lit > olen - o.op) return ST_CODEC;
+  const bool last = lz4_last(sc, lit, p, pend, o.op, olen);
+  if (last && (lit != pend - p || lit != olen - o.op)) return ST_CODEC;
   o.lit_global((gmem_u8*)in.g + p, lit);
   p += lit;
-  if (p == pend) {  // the last sequence carries literals only
+  if (last) {  // the last sequence carries literals only
     *ended = true;
     *pp = p;
     return ST_OK;
@@ -1495,7 +1532,7 @@ __device__ uint32_t lz4_one(InRing& in, uint32_t* pp, uint32_t pend, WaveOut<tru
       ml += b;
     } while (b == 255);
   }
-  if (ml > olen - o.op) return ST_CODEC;
+  if (ml > olen - o.op || !lz4_match_ends_ok(sc, token, off, ml, o.op, olen)) return ST_CODEC;
   while (ml) {
     const uint32_t m = min(ml, o.room());
     o.match(off, m);
@@ -1556,7 +1593,11 @@ __device__ uint32_t lz4_inflate(InRing& in, uint32_t p, uint32_t pend, WaveOut<t
     if (v0) seq_parse(in.ib, starts, s);
     const uint32_t len = v0 ? s.lit + s.ml : 0u;
     const uint32_t incl = wave_incl_scan(len), excl = incl - len;
-    const uint32_t cap = min(kChunk, olen - o.op);
+    // at most a chunk, and nothing that ends within the last 12 output bytes:
+    // a sequence the batch takes then satisfies both output-side end rules
+    // (lz4_shortcut), and the ones near the end go to lz4_one
+    const uint32_t left = olen - o.op;
+    const uint32_t cap = left >= 12 ? min(kChunk, left - 12) : 0u;
     const uint32_t dl = o.op + excl, dm = dl + s.lit;  // literal and match destinations
     const bool ok = v0 && incl <= cap && s.off != 0 && s.off <= dm;
     const uint64_t okm = __ballot(ok);
