@@ -256,9 +256,11 @@ sb_status sb_plan_status(sb_ctx* ctx, sb_plan* plan, int64_t* h_bad_page);
  * Utf8 offsets that start at 0).  Pages without a selected row are never
  * read: they need not be uploaded (packed = 1) and are not planned, staged
  * or decoded; a Utf8 column is therefore validated on its touched pages
- * only.  Flat leaves only (fixed width, Boolean, Binary / Utf8 / Large*):
- * selecting rows of a nested leaf needs per-level compaction of its offsets
- * and is not implemented (the callers' SB_E_NYI). */
+ * only.  Flat leaves (fixed width, Boolean, Binary / Utf8 / Large*) and one
+ * List / LargeList nest over a fixed-width leaf (the List section below: the
+ * selection is over the top-level rows).  Deeper chains, Struct / Map and
+ * Utf8 / Boolean leaves under a list need per-level compaction of their
+ * offsets and are not implemented (SB_E_NYI). */
 typedef struct sb_select sb_select;
 /* Resolves a selection against a column's pages (synchronous: k_sel_count +
  * one readback of 8 bytes per page).  d_selection: 4*ceil(n_rows/32) readable
@@ -298,6 +300,47 @@ sb_status sb_plan_selected_values_bytes(sb_ctx* ctx, sb_plan* plan, uint64_t* by
 /* Touched pages decoded in place / through scratch, and the plan's scratch bytes. */
 sb_status sb_plan_selected_stats(const sb_plan* plan, uint64_t* pages_direct, uint64_t* pages_compacted,
                                  uint64_t* scratch_bytes);
+
+/* Selective reads of a List<primitive> column (what sb_plan_list_column
+ * takes: one List / LargeList nest over a fixed-width leaf).  The selection
+ * is over the column's top-level rows; the result is the dense List array of
+ * the selected rows: k + 1 offsets from 0, list validity over the k rows, the
+ * rows' leaves back to back and their leaf validity, bit-exact with a full
+ * decode followed by a take (bytes under null leaves included; both bitmaps
+ * whole 32-bit words, zero past the last row / leaf).
+ *
+ * PageMeta.num_values of a nested page is its level count, so the selection
+ * cannot be resolved against the footer: it is resolved (sb_select_create)
+ * against metas whose num_values are the page ROWS, each page's first u32. */
+/* The rows of every page of a nested column chunk in HBM (synchronous: one
+ * small kernel and one readback of 4 bytes per page).  SB_E_IO names a page
+ * shorter than the 12-byte nested page header. */
+sb_status sb_list_page_rows(sb_ctx* ctx, const uint8_t* d_chunk, uint64_t chunk_len, const sb_page_meta* h_metas,
+                            uint64_t n_pages, uint64_t* h_rows);
+/* Plans the touched pages only (chunk layouts as sb_plan_selected_column).
+ * h_metas: the column's real metas (level counts); sel: resolved against the
+ * same pages with num_values = rows.  The plan's sizing pass decodes each
+ * touched page's rows and leaves: a page whose rows differ from the ones the
+ * selection was resolved with is SB_E_ARG, naming the first such page (the
+ * row counts are an unverified pre-read, and a wrong one would shift every
+ * later row).  On the plan: sb_plan_num_rows = the selected rows,
+ * sb_plan_num_pages = the touched pages, sb_plan_num_leaves = the touched
+ * pages' leaves -- a BOUND on the selected leaves, which only the decode
+ * learns: the caller allocates values and leaf validity for that many;
+ * sb_plan_status reports the first failing page by its index in the column;
+ * sb_plan_selected_stats = (0, touched pages, scratch bytes).  Every touched
+ * page decodes into plan-owned scratch through the ordinary list plan, then
+ * k_sel_take_list: an all-rows selection costs a full decode plus a take. */
+sb_status sb_plan_selected_list_column(sb_ctx* ctx, const sb_list_desc* desc, const sb_select* sel,
+                                       const sb_page_meta* h_metas, uint64_t n_pages, const uint8_t* d_chunk,
+                                       uint64_t chunk_len, int32_t packed, sb_plan** out);
+/* Asynchronous decode of such a plan (sb_decode_list_planned refuses it, and
+ * this call an ordinary list plan: SB_E_ARG).  Outputs as sb_list_out over
+ * sb_plan_num_rows rows and sb_plan_num_leaves leaves.  No row selected:
+ * offsets[0] = 0 and nothing else is launched. */
+sb_status sb_decode_list_selected(sb_ctx* ctx, sb_plan* plan, const sb_list_out* out);
+/* After a decode (waits for it): the leaves it wrote. */
+sb_status sb_plan_selected_leaves(sb_ctx* ctx, sb_plan* plan, uint64_t* leaves);
 
 /* ---- page-level unit entry points (synchronous) -------------------------
  * For a caller that walks the pages itself; the column decoders above fuse
@@ -601,6 +644,14 @@ uint64_t sb_file_num_columns(const sb_file* f);
 sb_status sb_file_column(const sb_file* f, uint64_t col, uint64_t* offset, uint64_t* chunk_len, uint64_t* n_pages,
                          const sb_page_meta** h_pages);
 sb_status sb_file_schema(const sb_file* f, const uint8_t** h_bytes, uint64_t* len);
+/* The rows of every page of nested leaf column `col` (each page's first u32;
+ * the footer's num_values of such a page is its level count), for resolving
+ * a row selection before anything is uploaded.  Host only; the cost is one
+ * 4-byte read per page at the page starts the footer gives.  cap: entries of
+ * h_rows (SB_E_ARG if the column has more pages).  SB_E_IO names a page
+ * shorter than the nested page header or one that starts past the end of the
+ * file. */
+sb_status sb_file_page_rows(sb_file* f, uint64_t col, uint64_t* h_rows, uint64_t cap);
 /* The NativeReader page source (reader.rs:60-131) as one staged copy: file
  * bytes [offset, offset + len) -> d_dst through the device's two pinned 16 MiB buffers
  * (parallel pread of chunk k+1 overlaps the DMA of chunk k on the device's

@@ -26,6 +26,6 @@ from .nested import (DeviceArray, Field, FieldDecoder, HostArray, ListColumnDeco
                      encode_list_column, encode_list_column_device)
 from .file import Leaf, StrawboatFile, parse_schema  # noqa: F401,E402
 from .table import ColumnGroupDecoder  # noqa: F401,E402
-from .select import (ResolvedSelection, SelectedBinaryDecoder, SelectedColumnDecoder, Selection,  # noqa: F401,E402
-                     normalize_ranges, page_runs, read_selected)
+from .select import (ResolvedSelection, SelectedBinaryDecoder, SelectedColumnDecoder, SelectedListDecoder,  # noqa: F401,E402
+                     Selection, list_page_rows, normalize_ranges, page_runs, read_selected, read_selected_list)
 from .stream import PageArray, decode_columns, iter_page_arrays, to_host  # noqa: F401,E402

@@ -37,6 +37,8 @@ EXPORTED = [
     "sb_select_create", "sb_select_num_rows", "sb_select_num_pages", "sb_select_page", "sb_select_destroy",
     "sb_plan_selected_column", "sb_decode_selected", "sb_decode_binary_selected", "sb_plan_selected_values_bytes",
     "sb_plan_selected_stats",
+    "sb_list_page_rows", "sb_file_page_rows", "sb_plan_selected_list_column", "sb_decode_list_selected",
+    "sb_plan_selected_leaves",
 ]
 
 MAX_NEST = 4
@@ -207,5 +209,16 @@ def lib():
     L.sb_plan_selected_values_bytes.restype = I32
     L.sb_plan_selected_stats.argtypes = [P, PU64, PU64, PU64]
     L.sb_plan_selected_stats.restype = I32
+    L.sb_list_page_rows.argtypes = [P, P, U64, ctypes.POINTER(PageMetaC), U64, PU64]
+    L.sb_list_page_rows.restype = I32
+    L.sb_file_page_rows.argtypes = [P, U64, PU64, U64]
+    L.sb_file_page_rows.restype = I32
+    # (sb_list_desc / sb_list_out: pa_amd.nested.ListDescC / ListOutC, by reference)
+    L.sb_plan_selected_list_column.argtypes = [P, P, P, ctypes.POINTER(PageMetaC), U64, P, U64, I32, PP]
+    L.sb_plan_selected_list_column.restype = I32
+    L.sb_decode_list_selected.argtypes = [P, P, P]
+    L.sb_decode_list_selected.restype = I32
+    L.sb_plan_selected_leaves.argtypes = [P, P, PU64]
+    L.sb_plan_selected_leaves.restype = I32
     _lib = L
     return L

@@ -97,6 +97,7 @@ struct sb_plan {
   uint16_t list_epoch = 0;  // tag of the last decode's block totals (k_list_bases)
   sb_plan* inner = nullptr;
   uint64_t n_leaves = 0;
+  std::vector<uint64_t> page_rows;  // list / nested plans: each page's top-level rows (the plan's sizing pass)
   int offset_width = 0;
   uint64_t* d_bin = nullptr;  // [sizes n | bases n | total 1 | UTF-8 flags 1] then BinLaunch::cls (u32)
   uint64_t* d_lb = nullptr;   // binary, every page staged: the fused pass's look-back states + counter
@@ -878,15 +879,42 @@ static sb_status list_launch(sb_ctx* ctx, sb_plan* p, const sb_list_out* out, in
   return SB_OK;
 }
 
+static sb_status plan_nested_pages(sb_ctx* ctx, const sb_nested_desc* d, const uint8_t* d_chunk, uint64_t chunk_len,
+                                   std::vector<sb::PageDesc> lpages, sb_plan** out, const uint32_t* ids);
+
+// The level pages as a page table (byte_off anywhere in the chunk: a
+// selective read plans its touched pages only); ids as in plan_pages.
+static sb_status plan_list_pages(sb_ctx* ctx, const sb_list_desc* d, const uint8_t* d_chunk, uint64_t chunk_len,
+                                 std::vector<sb::PageDesc> lpages, sb_plan** out, const uint32_t* ids = nullptr);
+
 sb_status sb_plan_list_column(sb_ctx* ctx, const sb_list_desc* d, const uint8_t* d_chunk, uint64_t chunk_len,
                               const sb_page_meta* h_metas, uint64_t n_pages, sb_plan** out) {
-  if (!ctx || !d || !out) return fail(ctx, SB_E_ARG, "null argument");
+  if (!ctx || !d || !out || (!h_metas && n_pages)) return fail(ctx, SB_E_ARG, "null argument");
   bool is_float;
   if (!type_width(d->physical_type, &is_float)) return fail(ctx, SB_E_NYI, "list leaf type %d not supported", d->physical_type);
   if (d->offset_width != 4 && d->offset_width != 8) return fail(ctx, SB_E_ARG, "offset width must be 4 or 8");
+  if (n_pages > 0xFFFFFFFFull) return fail(ctx, SB_E_ARG, "too many pages");
+  std::vector<sb::PageDesc> pages(n_pages);
+  uint64_t off = 0, levels = 0;
+  for (uint64_t i = 0; i < n_pages; i++) {
+    const sb_page_meta& m = h_metas[i];
+    if (m.length > 0xFFFFFFFFull || m.num_values > 0xFFFFFFFFull)
+      return fail(ctx, SB_E_ARG, "page %llu exceeds u32 sizes", (unsigned long long)i);
+    pages[i] = sb::PageDesc{off, levels, (uint32_t)m.length, (uint32_t)m.num_values, 0};
+    off += m.length;
+    levels += m.num_values;
+  }
+  return plan_list_pages(ctx, d, d_chunk, chunk_len, std::move(pages), out);
+}
+
+static sb_status plan_list_pages(sb_ctx* ctx, const sb_list_desc* d, const uint8_t* d_chunk, uint64_t chunk_len,
+                                 std::vector<sb::PageDesc> lpages, sb_plan** out, const uint32_t* ids) {
+  const uint64_t n_pages = lpages.size();
+  bool is_float;
+  (void)type_width(d->physical_type, &is_float);
   sb_column_desc cd{d->physical_type, 0};
   sb_plan* inner = nullptr;
-  sb_status st = plan_column(ctx, &cd, d_chunk, chunk_len, h_metas, n_pages, &inner, kRegionsBySize);
+  sb_status st = plan_pages(ctx, &cd, d_chunk, chunk_len, lpages, &inner, kRegionsBySize, ids);
   if (st) return st;
   // the inner plan's pages become the values streams only at decode time (its
   // plan-time Zstd scan read the list pages): keep the Zstd kernels
@@ -936,7 +964,8 @@ sb_status sb_plan_list_column(sb_ctx* ctx, const sb_list_desc* d, const uint8_t*
       nd.item_nullable = d->item_nullable;
       nd.offset_width = d->offset_width;
       sb_plan* w = nullptr;
-      const sb_status wst = sb_plan_nested_column(ctx, &nd, d_chunk, chunk_len, h_metas, n_pages, &w);
+      for (sb::PageDesc& pd : lpages) pd.row_off = 0;
+      const sb_status wst = plan_nested_pages(ctx, &nd, d_chunk, chunk_len, std::move(lpages), &w, ids);
       if (wst) return wst;
       w->list_walk = true;
       w->ldesc = *d;
@@ -946,10 +975,12 @@ sb_status sb_plan_list_column(sb_ctx* ctx, const sb_list_desc* d, const uint8_t*
     for (uint64_t i = 0; i < n_pages; i++) {
       if (stv[i]) {
         sb_plan_destroy(p);
-        return fail(ctx, (sb_status)stv[i], "page %llu: %s", (unsigned long long)i, sb_status_str((int)stv[i]));
+        return fail(ctx, (sb_status)stv[i], "page %llu: %s", (unsigned long long)(ids ? ids[i] : i),
+                    sb_status_str((int)stv[i]));
       }
       p->n_rows += exact[i] >> 32;
       p->n_leaves += exact[i] & 0xFFFFFFFFull;
+      p->page_rows.push_back(exact[i] >> 32);
     }
     // Do the page headers (rows, values usize) give the same counts?  Then
     // decodes size from them instead of walking every level twice.
@@ -969,6 +1000,7 @@ uint64_t sb_plan_num_leaves(const sb_plan* p) { return p ? p->n_leaves : 0; }
 
 sb_status sb_decode_list_planned(sb_ctx* ctx, sb_plan* p, const sb_list_out* out) {
   if (!ctx || !p || !out) return fail(ctx, SB_E_ARG, "null argument");
+  if (p->sel) return fail(ctx, SB_E_ARG, "selective plan: use sb_decode_list_selected");
   if (p->list_walk) {  // planned on the general walk: the same buffers as level 0 + the leaf
     sb_nested_out no{};
     no.d_offsets[0] = out->d_offsets;
@@ -1041,6 +1073,23 @@ static sb_status nest_launch(sb_ctx* ctx, sb_plan* p, const sb_nested_out* out, 
 sb_status sb_plan_nested_column(sb_ctx* ctx, const sb_nested_desc* d, const uint8_t* d_chunk, uint64_t chunk_len,
                                 const sb_page_meta* h_metas, uint64_t n_pages, sb_plan** out) {
   if (!ctx || !d || !out || (!h_metas && n_pages)) return fail(ctx, SB_E_ARG, "null argument");
+  if (n_pages > 0xFFFFFFFFull) return fail(ctx, SB_E_ARG, "too many pages");
+  std::vector<sb::PageDesc> lpages(n_pages);  // the level pages, back to back
+  uint64_t off = 0;
+  for (uint64_t i = 0; i < n_pages; i++) {
+    if (h_metas[i].length > 0xFFFFFFFFull || h_metas[i].num_values > 0xFFFFFFFFull || off + h_metas[i].length > chunk_len)
+      return fail(ctx, SB_E_ARG, "page %llu: bad size", (unsigned long long)i);
+    lpages[i] = sb::PageDesc{off, 0, (uint32_t)h_metas[i].length, (uint32_t)h_metas[i].num_values, 0};
+    off += h_metas[i].length;
+  }
+  return plan_nested_pages(ctx, d, d_chunk, chunk_len, std::move(lpages), out, nullptr);
+}
+
+// The level pages as a page table (plan_list_pages' fallback hands its own
+// on); ids as in plan_pages.
+static sb_status plan_nested_pages(sb_ctx* ctx, const sb_nested_desc* d, const uint8_t* d_chunk, uint64_t chunk_len,
+                                   std::vector<sb::PageDesc> lpages, sb_plan** out, const uint32_t* ids) {
+  const uint64_t n_pages = lpages.size();
   const int t = d->physical_type;
   bool is_float;
   const bool leaf_bin = t == SB_T_BINARY || t == SB_T_UTF8 || t == SB_T_LARGE_BINARY || t == SB_T_LARGE_UTF8;
@@ -1050,16 +1099,10 @@ sb_status sb_plan_nested_column(sb_ctx* ctx, const sb_nested_desc* d, const uint
   if (d->struct_mask < 0 || (d->struct_mask >> d->depth) != 0)
     return fail(ctx, SB_E_ARG, "struct mask 0x%x names nests past depth %d", (unsigned)d->struct_mask, d->depth);
   if (d->offset_width != 4 && d->offset_width != 8) return fail(ctx, SB_E_ARG, "offset width must be 4 or 8");
-  if (n_pages > 0xFFFFFFFFull) return fail(ctx, SB_E_ARG, "too many pages");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::vector<sb::PageDesc> lpages(n_pages);  // the level pages, back to back
-  uint64_t off = 0;
-  for (uint64_t i = 0; i < n_pages; i++) {
-    if (h_metas[i].length > 0xFFFFFFFFull || h_metas[i].num_values > 0xFFFFFFFFull || off + h_metas[i].length > chunk_len)
-      return fail(ctx, SB_E_ARG, "page %llu: bad size", (unsigned long long)i);
-    lpages[i] = sb::PageDesc{off, 0, (uint32_t)h_metas[i].length, (uint32_t)h_metas[i].num_values, 0};
-    off += h_metas[i].length;
-  }
+  for (uint64_t i = 0; i < n_pages; i++)
+    if (lpages[i].byte_off + lpages[i].byte_len > chunk_len)
+      return fail(ctx, SB_E_ARG, "page %llu: bad size", (unsigned long long)(ids ? ids[i] : i));
   sb_plan* p = new sb_plan();
   p->desc = sb_column_desc{t, 0};
   p->nested = true;
@@ -1097,8 +1140,10 @@ sb_status sb_plan_nested_column(sb_ctx* ctx, const sb_nested_desc* d, const uint
     for (uint64_t i = 0; i < n_pages; i++) {
       if (stv[i]) {
         sb_plan_destroy(p);
-        return fail(ctx, (sb_status)stv[i], "page %llu: %s", (unsigned long long)i, sb_status_str((int)stv[i]));
+        return fail(ctx, (sb_status)stv[i], "page %llu: %s", (unsigned long long)(ids ? ids[i] : i),
+                    sb_status_str((int)stv[i]));
       }
+      p->page_rows.push_back(cnt[i * (D + 1)]);
       for (uint64_t k = 0; k <= D; k++) {
         bases[i * (D + 1) + k] = p->nest_totals[k];
         p->nest_totals[k] += cnt[i * (D + 1) + k];
@@ -1115,7 +1160,7 @@ sb_status sb_plan_nested_column(sb_ctx* ctx, const sb_nested_desc* d, const uint
     }
   }
   const sb_column_desc cd{t, 0};
-  sb_status st = plan_pages(ctx, &cd, d_chunk, chunk_len, std::move(vpages), &p->inner);
+  sb_status st = plan_pages(ctx, &cd, d_chunk, chunk_len, std::move(vpages), &p->inner, kRegionsProbe, ids);
   if (st) {
     sb_plan_destroy(p);
     return st;
@@ -1280,8 +1325,12 @@ struct SelState {
   uint64_t* d_tile_bytes = nullptr;            // binary: [n_tiles + 1]
   uint8_t* s_values = nullptr;                 // decoded rows of the part pages
   uint8_t* s_validity = nullptr;
-  uint8_t* s_aux = nullptr;                    // binary: offsets
+  uint8_t* s_aux = nullptr;                    // binary / list: offsets
   uint64_t s_values_len = 0;
+  // List<primitive> (sb_plan_selected_list_column): `part` is a list plan over
+  // the touched pages, s_values its leaves, s_validity the list validity
+  bool list = false;
+  uint8_t* s_leaf_validity = nullptr;
 };
 
 static void sel_destroy(SelState* s) {
@@ -1492,6 +1541,7 @@ sb_status sb_decode_selected(sb_ctx* ctx, sb_plan* p, const sb_primitive_out* ou
   if (!ctx || !p || !out) return SB_E_ARG;
   if (!p->sel) return fail(ctx, SB_E_ARG, "not a selective plan");
   if (p->binary) return fail(ctx, SB_E_ARG, "binary plan: use sb_decode_binary_selected");
+  if (p->sel->list) return fail(ctx, SB_E_ARG, "list plan: use sb_decode_list_selected");
   if (!p->n_rows) return SB_OK;  // no row selected: no page, no launch
   if (!out->d_values) return fail(ctx, SB_E_ARG, "values buffer is null");
   if (p->desc.nullable && !out->d_validity) return fail(ctx, SB_E_ARG, "validity buffer is null");
@@ -1573,6 +1623,7 @@ sb_status sb_decode_binary_selected(sb_ctx* ctx, sb_plan* p, const sb_binary_out
 sb_status sb_plan_selected_values_bytes(sb_ctx* ctx, sb_plan* p, uint64_t* bytes) {
   if (!ctx || !p || !bytes) return SB_E_ARG;
   if (!p->sel) return fail(ctx, SB_E_ARG, "not a selective plan");
+  if (p->sel->list) return fail(ctx, SB_E_ARG, "list plan: use sb_plan_selected_leaves");
   *bytes = 0;
   if (!p->binary) {
     *bytes = p->boolean ? (p->n_rows + 31) / 32 * 4 : p->n_rows * (uint64_t)p->width;
@@ -1592,6 +1643,220 @@ sb_status sb_plan_selected_stats(const sb_plan* p, uint64_t* pages_direct, uint6
   if (pages_direct) *pages_direct = p->sel->direct_ids.size();
   if (pages_compacted) *pages_compacted = p->sel->part_ids.size();
   if (scratch_bytes) *scratch_bytes = p->sel->scratch_bytes;
+  return SB_OK;
+}
+
+// ---- selective reads of List<primitive> columns -----------------------------
+// The footer's num_values of a nested page is its level count; its rows are
+// the page's first u32.  A row selection is resolved against those.
+sb_status sb_list_page_rows(sb_ctx* ctx, const uint8_t* d_chunk, uint64_t chunk_len, const sb_page_meta* h_metas,
+                            uint64_t n_pages, uint64_t* h_rows) {
+  if (!ctx || (n_pages && (!d_chunk || !h_metas || !h_rows))) return fail(ctx, SB_E_ARG, "null argument");
+  if (n_pages > 0xFFFFFFFFull) return fail(ctx, SB_E_ARG, "too many pages");
+  if (!n_pages) return SB_OK;
+  std::vector<uint64_t> offs(n_pages);
+  uint64_t off = 0;
+  for (uint64_t i = 0; i < n_pages; i++) {
+    if (h_metas[i].length > chunk_len || off > chunk_len - h_metas[i].length)
+      return fail(ctx, SB_E_ARG, "page %llu overruns the column chunk", (unsigned long long)i);
+    if (h_metas[i].length < 12)
+      return fail(ctx, SB_E_IO, "page %llu: %llu bytes, shorter than a nested page's header", (unsigned long long)i,
+                  (unsigned long long)h_metas[i].length);
+    offs[i] = off;
+    off += h_metas[i].length;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<uint32_t> rows(n_pages);
+  uint8_t* d = nullptr;  // [page offsets n (u64) | rows n (u32)]
+  hipError_t e = hipMalloc(&d, n_pages * (sizeof(uint64_t) + sizeof(uint32_t)));
+  uint32_t* d_rows = (uint32_t*)(d + n_pages * sizeof(uint64_t));
+  if (e == hipSuccess) e = hipMemcpyAsync(d, offs.data(), n_pages * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && sb::launch_list_page_rows(d_chunk, (const uint64_t*)d, (uint32_t)n_pages, d_rows, ctx->stream))
+    e = hipErrorLaunchFailure;
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(rows.data(), d_rows, n_pages * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (d) (void)hipFree(d);
+  if (e != hipSuccess) return fail(ctx, SB_E_DEVICE, "page rows: %s", hipGetErrorString(e));
+  for (uint64_t i = 0; i < n_pages; i++) h_rows[i] = rows[i];
+  return SB_OK;
+}
+
+sb_status sb_plan_selected_list_column(sb_ctx* ctx, const sb_list_desc* d, const sb_select* sel,
+                                       const sb_page_meta* h_metas, uint64_t n_pages, const uint8_t* d_chunk,
+                                       uint64_t chunk_len, int32_t packed, sb_plan** out) {
+  if (!ctx || !d || !sel || !out || (!h_metas && n_pages)) return fail(ctx, SB_E_ARG, "null argument");
+  bool is_float;
+  const int width = type_width(d->physical_type, &is_float);
+  if (!width) return fail(ctx, SB_E_NYI, "list leaf type %d not supported", d->physical_type);
+  if (d->offset_width != 4 && d->offset_width != 8) return fail(ctx, SB_E_ARG, "offset width must be 4 or 8");
+  if (n_pages != sel->metas.size())
+    return fail(ctx, SB_E_ARG, "the column has %llu pages, the selection was resolved against %llu",
+                (unsigned long long)n_pages, (unsigned long long)sel->metas.size());
+  if (!d_chunk && !sel->touched.empty()) return fail(ctx, SB_E_ARG, "null column chunk");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint64_t ow = (uint64_t)d->offset_width;
+
+  // The touched level pages (both chunk layouts differ only in byte_off) and
+  // their rows: every touched page decodes into scratch.
+  std::vector<sb::PageDesc> part;
+  std::vector<uint32_t> part_ids;
+  std::vector<sb::SelPage> sp;
+  std::vector<uint32_t> tiles;
+  uint64_t col_off = 0, packed_off = 0, col_row = 0, out_row = 0, part_rows = 0, levels = 0;
+  for (uint64_t i = 0; i < n_pages; i++) {
+    const sb_page_meta& m = h_metas[i];
+    const uint64_t rows = sel->metas[i].num_values, cnt = sel->counts[i];
+    if (m.length != sel->metas[i].length)
+      return fail(ctx, SB_E_ARG, "page %llu: the selection was resolved against a page of another length",
+                  (unsigned long long)i);
+    if (m.length > 0xFFFFFFFFull || m.num_values > 0xFFFFFFFFull)
+      return fail(ctx, SB_E_ARG, "page %llu exceeds u32 sizes", (unsigned long long)i);
+    if (cnt) {
+      part.push_back(sb::PageDesc{packed ? packed_off : col_off, levels, (uint32_t)m.length, (uint32_t)m.num_values, 0});
+      part_ids.push_back((uint32_t)i);
+      const uint32_t nt = (uint32_t)((rows + sb::kSelTileRows - 1) / sb::kSelTileRows);
+      for (uint32_t t = 0; t < nt; t++) {
+        tiles.push_back((uint32_t)sp.size());
+        tiles.push_back(t);
+      }
+      sp.push_back(sb::SelPage{col_row, part_rows, out_row, (uint32_t)rows, 0});
+      part_rows += rows;
+      levels += m.num_values;
+      packed_off += m.length;
+      out_row += cnt;
+    }
+    col_off += m.length;
+    col_row += rows;
+  }
+  if (tiles.size() / 2 > 0x7FFFFFFFull) return fail(ctx, SB_E_ARG, "too many pages");
+
+  SelState* s = new SelState();
+  sb_plan* p = new sb_plan();
+  p->sel = s;
+  s->list = true;
+  s->part_ids = std::move(part_ids);
+  s->part_rows = part_rows;
+  s->n_tiles = (uint32_t)(tiles.size() / 2);
+  s->d_sel = (const uint32_t*)sel->d_selection;
+  p->desc = sb_column_desc{d->physical_type, 0};
+  p->ldesc = *d;
+  p->d_chunk = d_chunk;
+  p->chunk_len = chunk_len;
+  p->width = width;
+  p->is_float = is_float;
+  p->offset_width = d->offset_width;
+  p->n_rows = sel->n_selected;
+  p->n_pages = sel->touched.size();
+  if (part.empty()) {
+    *out = p;
+    return SB_OK;
+  }
+  sb_status st = plan_list_pages(ctx, d, d_chunk, chunk_len, std::move(part), &s->part, s->part_ids.data());
+  if (st) {
+    sb_plan_destroy(p);
+    return st;
+  }
+  // The selection was resolved against row counts from an unverified
+  // pre-read; the sizing pass above decoded the real ones.  A page that
+  // differs would shift every later row.
+  for (size_t j = 0; j < s->part_ids.size(); j++) {
+    const uint32_t id = s->part_ids[j];
+    if (s->part->page_rows[j] != sel->metas[id].num_values) {
+      const unsigned long long got = s->part->page_rows[j], want = sel->metas[id].num_values;
+      sb_plan_destroy(p);
+      return fail(ctx, SB_E_ARG, "page %u: it decodes to %llu rows, the selection was resolved with %llu", id, got,
+                  want);
+    }
+  }
+  p->n_leaves = s->part->n_leaves;  // the bound: the touched pages' leaves
+  // scratch: [SelPage table | tile list | tile bases | leaves | leaf validity | list validity | offsets]
+  const uint64_t b_sp = sb::align16(sp.size() * sizeof(sb::SelPage));
+  const uint64_t b_tiles = sb::align16(tiles.size() * sizeof(uint32_t));
+  const uint64_t b_tb = sb::align16((s->n_tiles + 1ull) * sizeof(uint64_t));
+  s->s_values_len = p->n_leaves;  // (in leaves)
+  const uint64_t b_values = sb::align16(p->n_leaves * (uint64_t)width) + 16;
+  const uint64_t b_leafv = d->item_nullable ? sb::align16(4 * ((p->n_leaves + 31) / 32)) + 16 : 0;
+  const uint64_t b_listv = d->list_nullable ? sb::align16(4 * ((part_rows + 31) / 32)) + 16 : 0;
+  const uint64_t b_offs = sb::align16((part_rows + 1) * ow);
+  s->scratch_bytes = b_sp + b_tiles + b_tb + b_values + b_leafv + b_listv + b_offs;
+  hipError_t e = hipMalloc(&s->d_scratch, s->scratch_bytes);
+  if (e == hipSuccess) {
+    uint8_t* q = s->d_scratch;
+    s->d_sp = (sb::SelPage*)q, q += b_sp;
+    s->d_tiles = (uint32_t*)q, q += b_tiles;
+    s->d_tile_bytes = (uint64_t*)q, q += b_tb;
+    s->s_values = q, q += b_values;
+    if (d->item_nullable) s->s_leaf_validity = q, q += b_leafv;
+    if (d->list_nullable) s->s_validity = q, q += b_listv;
+    s->s_aux = q;
+    e = hipMemcpyAsync(s->d_sp, sp.data(), sp.size() * sizeof(sb::SelPage), hipMemcpyHostToDevice, ctx->stream);
+  }
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(s->d_tiles, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // host vectors go out of scope
+  if (e != hipSuccess) {
+    sb_plan_destroy(p);
+    return fail(ctx, SB_E_DEVICE, "selective list plan scratch: %s", hipGetErrorString(e));
+  }
+  *out = p;
+  return SB_OK;
+}
+
+sb_status sb_decode_list_selected(sb_ctx* ctx, sb_plan* p, const sb_list_out* out) {
+  if (!ctx || !p || !out) return fail(ctx, SB_E_ARG, "null argument");
+  if (!p->sel || !p->sel->list) return fail(ctx, SB_E_ARG, "not a selective list plan");
+  if (!out->d_offsets) return fail(ctx, SB_E_ARG, "offsets buffer is null");
+  if ((uintptr_t)out->d_offsets % p->offset_width) return fail(ctx, SB_E_ARG, "offsets buffer is not aligned");
+  SelState* s = p->sel;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!s->part) {  // no row selected: offsets [0]
+    HIP_TRY(ctx, hipMemsetAsync(out->d_offsets, 0, (size_t)p->offset_width, ctx->stream));
+    return SB_OK;
+  }
+  if (p->n_leaves && !out->d_values) return fail(ctx, SB_E_ARG, "values buffer is null");
+  if ((uintptr_t)out->d_values % p->width) return fail(ctx, SB_E_ARG, "values buffer is not aligned");
+  if (p->ldesc.list_nullable && !out->d_list_validity) return fail(ctx, SB_E_ARG, "list validity is null");
+  if (p->ldesc.item_nullable && p->n_leaves && !out->d_leaf_validity) return fail(ctx, SB_E_ARG, "leaf validity is null");
+  if (p->ldesc.list_nullable)
+    HIP_TRY(ctx, hipMemsetAsync(out->d_list_validity, 0, (p->n_rows + 31) / 32 * 4, ctx->stream));
+  if (p->ldesc.item_nullable && p->n_leaves)
+    HIP_TRY(ctx, hipMemsetAsync(out->d_leaf_validity, 0, (p->n_leaves + 31) / 32 * 4, ctx->stream));
+  const sb_list_out so{s->s_aux, s->s_validity, s->s_values, s->s_leaf_validity};
+  const sb_status st = sb_decode_list_planned(ctx, s->part, &so);
+  if (st) return st;
+  sb::SelList l{};
+  l.b.sel = s->d_sel;
+  l.b.pages = s->d_sp;
+  l.b.tiles = s->d_tiles;
+  l.b.n_tiles = s->n_tiles;
+  l.b.src_offsets = s->s_aux;
+  l.b.src_values = s->s_values;
+  l.b.src_len = s->s_values_len;
+  l.b.src_validity = p->ldesc.list_nullable ? (const uint32_t*)s->s_validity : nullptr;
+  l.b.dst_offsets = (uint8_t*)out->d_offsets;
+  l.b.dst_values = (uint8_t*)out->d_values;
+  l.b.values_cap = p->n_leaves;
+  l.b.dst_validity = (uint32_t*)out->d_list_validity;
+  l.b.tile_bytes = s->d_tile_bytes;
+  if (p->ldesc.item_nullable && p->n_leaves) {
+    l.src_leaf_validity = (const uint32_t*)s->s_leaf_validity;
+    l.dst_leaf_validity = (uint32_t*)out->d_leaf_validity;
+  }
+  if (sb::launch_sel_take_list(p->offset_width, p->width, l, ctx->stream))
+    return fail(ctx, SB_E_DEVICE, "list take launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return SB_OK;
+}
+
+sb_status sb_plan_selected_leaves(sb_ctx* ctx, sb_plan* p, uint64_t* leaves) {
+  if (!ctx || !p || !leaves) return fail(ctx, SB_E_ARG, "null argument");
+  if (!p->sel || !p->sel->list) return fail(ctx, SB_E_ARG, "not a selective list plan");
+  *leaves = 0;
+  if (!p->sel->part) return SB_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipMemcpyAsync(leaves, p->sel->d_tile_bytes + p->sel->n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost,
+                              ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return SB_OK;
 }
 

@@ -398,6 +398,25 @@ sb_status sb_file_schema(const sb_file* f, const uint8_t** h_bytes, uint64_t* le
   return SB_OK;
 }
 
+sb_status sb_file_page_rows(sb_file* f, uint64_t col, uint64_t* h_rows, uint64_t cap) {
+  if (!f || col >= f->col_off.size()) return SB_E_ARG;
+  const uint64_t a = f->col_start[col], b = f->col_start[col + 1];
+  if (b - a > cap || (b > a && !h_rows)) return file_fail(f, SB_E_ARG, "page rows: buffer too small");
+  uint64_t pos = f->col_off[col];
+  for (uint64_t i = a; i < b; i++) {
+    const uint64_t len = f->pages[i].length;
+    const std::string page = "page " + std::to_string(i - a);
+    if (len < 12) return file_fail(f, SB_E_IO, page + ": shorter than a nested page's header");
+    if (pos > f->size || f->size - pos < 4) return file_fail(f, SB_E_IO, page + " starts past the end of the file");
+    uint8_t w[4];
+    if (!pread_all(f->fd, w, 4, pos)) return file_fail(f, SB_E_IO, page + ": short read");
+    h_rows[i - a] = (uint64_t)w[0] | (uint64_t)w[1] << 8 | (uint64_t)w[2] << 16 | (uint64_t)w[3] << 24;
+    if (len > f->size) return file_fail(f, SB_E_IO, page + " reaches past the end of the file");
+    pos += len;
+  }
+  return SB_OK;
+}
+
 // File bytes [offset, offset + len) -> d_dst, through the device's two
 // pinned buffers: the pread of chunk k+1 (kReadThreads workers) overlaps the
 // DMA of chunk k on the staging copy stream; the context's stream waits for the last copy,

@@ -289,7 +289,7 @@ struct NestLaunch {
 int launch_nest(int stage, const NestLaunch& a, void* stream);
 
 // Selective reads (sb_select.hip): a selection is an LSB-first bitmap over a
-// flat column's rows.  A compacted page: its rows [sel_row, + num_values) of
+// column's rows (a List column's top-level rows).  A compacted page: its rows [sel_row, + num_values) of
 // the column (its selection bits), decoded at rows src_row.. of the plan's
 // scratch, its selected rows appended at dst_row of the output.
 struct SelPage {
@@ -332,5 +332,17 @@ struct SelBin {
 };
 // Sizing pass, scan and take pass of a Binary / Utf8 column (three launches).
 int launch_sel_take_bin(int offset_width, const SelBin& a, void* stream);
+// A List<primitive> column is the same shape with leaves of `width` bytes in
+// place of bytes (src_len, values_cap and tile_bytes count leaves), plus the
+// leaf validity bits of each selected row.
+struct SelList {
+  SelBin b;                           // src / dst validity: the list validity
+  const uint32_t* src_leaf_validity;  // over the scratch leaves, or nullptr
+  uint32_t* dst_leaf_validity;        // zeroed by the host over the leaf bound
+};
+// Sizing pass, scan and take pass of a List column (three launches).
+int launch_sel_take_list(int offset_width, int width, const SelList& a, void* stream);
+// rows[i] = the u32 at byte offs[i] of the chunk (a nested page's row count).
+int launch_list_page_rows(const uint8_t* chunk, const uint64_t* offs, uint32_t n_pages, uint32_t* rows, void* stream);
 
 }  // namespace sb

@@ -1,8 +1,10 @@
 // sb_select.hip -- row selection over decoded pages (selective reads).
 //
-// A selection is an LSB-first Arrow bitmap over a flat column's rows.  The
-// host (sb_api.cpp, sb_plan_selected_column) decodes the partially selected
-// pages into plan-owned scratch with the ordinary page kernels; the kernels
+// A selection is an LSB-first Arrow bitmap over a column's rows (a List
+// column's top-level rows).  The host (sb_api.cpp, sb_plan_selected_column,
+// sb_plan_selected_list_column) decodes the partially selected pages (Binary
+// and List: every touched page) into plan-owned scratch with the ordinary
+// page kernels; the kernels
 // here turn "rows I want" into per-page work and dense Arrow buffers:
 //
 //   k_sel_count     selected rows of every page (popcount of its bit range)
@@ -12,6 +14,15 @@
 //   k_sel_bin_size / k_sel_scan / k_sel_take_bin<OW>
 //                   Binary / Utf8: selected bytes per tile, their scan into
 //                   each tile's values base, then offsets + bytes + validity
+//   k_sel_take_list<OW, W>
+//                   List<primitive>: the same three passes with leaves of W
+//                   bytes in place of bytes (the sizing pass and the scan are
+//                   the Binary ones), plus the selected rows' leaf validity
+//                   bits, a bit-range copy at arbitrary bit offsets
+//   k_list_page_rows
+//                   the row count every nested page starts with (a List
+//                   selection is resolved against these, not the footer's
+//                   level counts)
 //
 // Take grids are one 256-thread workgroup per (page, tile of kSelTileRows
 // rows); each wave owns a quarter of the tile and walks it in 64-row groups:
@@ -364,6 +375,148 @@ __global__ __launch_bounds__(kSelNT) void k_sel_take_bin(SelBin a) {
   if (a.src_validity) image_flush(img, out0, t.tile_cnt, a.dst_validity, tid);
 }
 
+// OR the low cnt (1..64) bits of v into a global bitmap at bit position pos:
+// three lanes, one word each.  Every output bit has one writer, so a word all
+// of whose bits this call owns has no other writer and is stored plainly; the
+// rest are ORed into the bitmap the host zeroed.
+__device__ __forceinline__ void bits_out(uint32_t* out, uint64_t pos, uint64_t v, uint32_t cnt, uint32_t lane) {
+  if (lane >= 3 || !cnt) return;
+  const uint32_t s = (uint32_t)(pos & 31);
+  const uint64_t own = cnt >= 64 ? ~0ull : (1ull << cnt) - 1;
+  v &= own;
+  const uint64_t vlo = v << s, olo = own << s;
+  const uint32_t vhi = s ? (uint32_t)(v >> (64 - s)) : 0u, ohi = s ? (uint32_t)(own >> (64 - s)) : 0u;
+  const uint32_t w = lane == 0 ? (uint32_t)vlo : lane == 1 ? (uint32_t)(vlo >> 32) : vhi;
+  const uint32_t o = lane == 0 ? (uint32_t)olo : lane == 1 ? (uint32_t)(olo >> 32) : ohi;
+  uint32_t* p = out + (pos >> 5) + lane;
+  if (o == 0xFFFFFFFFu) *p = w;
+  else if (w) atomicOr(p, w);
+}
+
+// List<primitive>: k_sel_take_bin with leaves of W bytes in place of bytes
+// (a.b counts leaves), and the leaf validity bits of the copied leaves.  A
+// tile's leaves are unbounded, so their bits take no LDS image: each step of
+// the two copy loops ballots the source bits of its (up to 64) leaves and
+// writes them at their output bit position (bits_out).
+template <int OW, int W>
+__global__ __launch_bounds__(kSelNT) void k_sel_take_list(SelList l) {
+  using O = typename off_of<OW>::type;
+  using T = typename word_of<W>::type;
+  const SelBin& a = l.b;
+  __shared__ uint32_t red[4], wtot[4];
+  __shared__ uint64_t wleaves[4];
+  __shared__ uint32_t img[kImageWords];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (uint32_t i = tid; i < kImageWords; i += kSelNT) img[i] = 0;
+  const TileWalk t = tile_walk(a.sel, a.pages, a.tiles, red, wtot);
+  if (!t.tile_cnt) return;
+  const uint64_t out0 = t.sp.dst_row + t.tile_base;
+  const uint32_t bit0 = (uint32_t)(out0 & 31);
+  const uint64_t src_end = t.sp.src_row + t.sp.num_values;
+  const T* sv = (const T*)a.src_values;
+  T* dv = (T*)a.dst_values;
+  const uint32_t* sbits = l.src_leaf_validity;
+  // selected leaves of this wave's rows -> its values base
+  uint64_t wsum = 0;
+  for (uint32_t g = 0; g < kSelGroups; g++) {
+    const uint64_t mg = __shfl(t.m, g);
+    uint64_t first;
+    if ((mg >> lane) & 1) wsum += row_len<OW>(a, t.sp.src_row + (t.w0 + 64ull * g + lane - t.p0), &first);
+  }
+  for (int o = 32; o; o >>= 1) wsum += __shfl_xor(wsum, o);
+  if (lane == 0) wleaves[wave] = wsum;
+  __syncthreads();
+  uint64_t base = a.tile_bytes[blockIdx.x];
+  for (uint32_t w = 0; w < wave; w++) base += wleaves[w];
+  for (uint32_t g = 0; g < kSelGroups; g++) {
+    const uint64_t mg = __shfl(t.m, g);
+    if (!mg) continue;
+    const uint32_t cnt = (uint32_t)__popcll(mg);
+    const uint32_t orel = t.wave_base + __shfl(t.excl, g);
+    const uint64_t s0 = t.sp.src_row + (t.w0 + 64ull * g - t.p0);
+    const bool on = (mg >> lane) & 1;
+    uint64_t first = 0;
+    const uint64_t len = on ? row_len<OW>(a, s0 + lane, &first) : 0ull;
+    uint64_t inc = len;
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+      const uint64_t u = __shfl_up(inc, o);
+      if (lane >= o) inc += u;
+    }
+    const uint64_t dst = base + inc - len;  // this row's first output leaf
+    base += __shfl(inc, 63);
+    if (on) ((O*)a.dst_offsets)[out0 + orel + lane_rank(mg) + 1] = (O)(dst + len);
+    const bool fits = dst + len <= a.values_cap;
+    // short rows, packed: output leaf b of the group's short rows belongs to
+    // the last lane whose prefix is <= b (empty rows share their successor's)
+    const uint32_t plen = on && fits && len <= kSelLongRow ? (uint32_t)len : 0u;
+    uint32_t pinc = plen;
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+      const uint32_t u = __shfl_up(pinc, o);
+      if (lane >= o) pinc += u;
+    }
+    const uint32_t pex = pinc - plen, ptot = __shfl(pinc, 63);
+    for (uint32_t b0 = 0; b0 < ptot; b0 += 64) {
+      const uint32_t b = b0 + lane;
+      uint32_t r = 0;
+#pragma unroll
+      for (uint32_t s = 32; s; s >>= 1) {
+        const uint32_t cand = r + s;
+        const uint32_t pv = __shfl(pex, cand & 63);
+        if (cand < 64 && pv <= b) r = cand;
+      }
+      const uint32_t k = b - __shfl(pex, r);
+      const uint64_t src = __shfl(first, r) + k, d = __shfl(dst, r) + k;
+      const bool act = b < ptot;
+      if (act) dv[d] = sv[src];
+      if (sbits) {
+        // the step's output leaves are consecutive except where a long row
+        // (or one that does not fit) lies between two short ones: one
+        // bits_out per consecutive run
+        const uint64_t vb = __ballot(act && ((sbits[src >> 5] >> (src & 31)) & 1));
+        const uint64_t dprev = __shfl_up(d, 1);
+        uint64_t starts = __ballot(act && (lane == 0 || d != dprev + 1));
+        const uint32_t nact = min(64u, ptot - b0);
+        while (starts) {
+          const uint32_t s = (uint32_t)__builtin_ctzll(starts);
+          starts &= starts - 1;
+          const uint32_t e = starts ? (uint32_t)__builtin_ctzll(starts) : nact;
+          bits_out(l.dst_leaf_validity, __shfl(d, s), vb >> s, e - s, lane);
+        }
+      }
+    }
+    // long rows: the whole wave copies one, 64 leaves a step
+    for (uint64_t big = __ballot(on && fits && len > kSelLongRow); big; big &= big - 1) {
+      const uint32_t r = (uint32_t)__builtin_ctzll(big);
+      const uint64_t rs = __shfl(first, r), rd = __shfl(dst, r), rl = __shfl(len, r);
+      for (uint64_t i0 = 0; i0 < rl; i0 += 64) {
+        const uint64_t i = i0 + lane;
+        const bool act = i < rl;
+        if (act) dv[rd + i] = sv[rs + i];
+        if (sbits) {
+          const uint64_t vb = __ballot(act && ((sbits[(rs + i) >> 5] >> ((rs + i) & 31)) & 1));
+          bits_out(l.dst_leaf_validity, rd + i0, vb, (uint32_t)min((uint64_t)64, rl - i0), lane);
+        }
+      }
+    }
+    if (a.src_validity) {
+      const uint64_t c = wave_compress(bits64(a.src_validity, s0, src_end), mg, cnt, lane);
+      image_or(img, bit0 + orel, c, lane);
+    }
+  }
+  __syncthreads();
+  if (a.src_validity) image_flush(img, out0, t.tile_cnt, a.dst_validity, tid);
+}
+
+// A nested page starts with its row count (pages start at any byte).
+__global__ __launch_bounds__(256) void k_list_page_rows(const uint8_t* __restrict__ chunk,
+                                                        const uint64_t* __restrict__ offs, uint32_t n_pages,
+                                                        uint32_t* __restrict__ rows) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_pages) return;
+  const uint8_t* p = chunk + offs[i];
+  rows[i] = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
+
 }  // namespace
 
 int launch_sel_count(const uint32_t* sel, const uint64_t* row_offs, uint32_t n_pages, uint64_t* counts, void* stream) {
@@ -402,6 +555,36 @@ int launch_sel_take_bin(int offset_width, const SelBin& a, void* stream) {
   if (offset_width == 4) return take_bin<4>(a, (hipStream_t)stream);
   if (offset_width == 8) return take_bin<8>(a, (hipStream_t)stream);
   return 1;
+}
+
+// The sizing pass and the scan are the Binary ones (offsets count leaves).
+template <int OW>
+static int take_list(int width, const SelList& a, hipStream_t s) {
+  const dim3 grid(a.b.n_tiles), block(kSelNT);
+  hipLaunchKernelGGL(k_sel_bin_size<OW>, grid, block, 0, s, a.b);
+  hipLaunchKernelGGL(k_sel_scan<OW>, dim3(1), dim3(64), 0, s, a.b);
+  switch (width) {
+    case 1: hipLaunchKernelGGL((k_sel_take_list<OW, 1>), grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((k_sel_take_list<OW, 2>), grid, block, 0, s, a); break;
+    case 4: hipLaunchKernelGGL((k_sel_take_list<OW, 4>), grid, block, 0, s, a); break;
+    case 8: hipLaunchKernelGGL((k_sel_take_list<OW, 8>), grid, block, 0, s, a); break;
+    default: return 1;
+  }
+  return hipGetLastError() != hipSuccess;
+}
+
+int launch_sel_take_list(int offset_width, int width, const SelList& a, void* stream) {
+  if (!a.b.n_tiles) return 0;
+  if (offset_width == 4) return take_list<4>(width, a, (hipStream_t)stream);
+  if (offset_width == 8) return take_list<8>(width, a, (hipStream_t)stream);
+  return 1;
+}
+
+int launch_list_page_rows(const uint8_t* chunk, const uint64_t* offs, uint32_t n_pages, uint32_t* rows, void* stream) {
+  if (!n_pages) return 0;
+  hipLaunchKernelGGL(k_list_page_rows, dim3((n_pages + 255) / 256), dim3(256), 0, (hipStream_t)stream, chunk, offs,
+                     n_pages, rows);
+  return hipGetLastError() != hipSuccess;
 }
 
 }  // namespace sb

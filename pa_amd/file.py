@@ -221,10 +221,36 @@ class StrawboatFile:
         (pa_amd.Selection) names: only the runs of touched pages are uploaded
         (their bytes: last_uploaded_bytes) and decoded.  Fixed width /
         Boolean -> (values, validity), Binary / Utf8 -> (offsets, values,
-        validity).  A nested leaf raises StrawboatError(E_NYI)."""
+        validity).  A nested leaf raises StrawboatError(E_NYI): a List
+        column is read with read_selected_list."""
         from .select import file_read_selected
 
         return file_read_selected(self, col, selection, ctx)
+
+    def page_rows(self, col: int) -> List[int]:
+        """The top-level rows of every page of leaf column `col` (host only).
+        A flat leaf: the footer's num_values.  A nested leaf, whose footer
+        num_values are level counts: each page's first u32, one 4-byte read
+        per page (sb_file_page_rows)."""
+        if not 0 <= col < self.num_columns or len(self.leaves) != self.num_columns:
+            raise N.StrawboatError(N.E_ARG, f"column {col} out of range")
+        if not self.leaves[col].depth:
+            return [m.num_values for m in self.columns[col].pages]
+        _, _, npg, _ = self._column(col)
+        rows = (ctypes.c_uint64 * max(1, npg))()
+        self._check(N.lib().sb_file_page_rows(self._h, col, rows, npg))
+        return [int(rows[i]) for i in range(npg)]
+
+    def read_selected_list(self, col: int, selection, ctx: Optional[Context] = None):
+        """The top-level rows of List / LargeList leaf column `col` (one list
+        nest over a fixed-width leaf) that `selection` names, as a dense List
+        array: (offsets, list validity | None, values, leaf validity | None).
+        The page rows are read from the file (page_rows), only the runs of
+        touched pages are uploaded (their bytes: last_uploaded_bytes) and
+        decoded.  Any other leaf raises StrawboatError(E_NYI)."""
+        from .select import file_read_selected_list
+
+        return file_read_selected_list(self, col, selection, ctx)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -178,6 +178,19 @@ class ListColumnDecoder:
         dec.shard = shard
         return dec
 
+    @classmethod
+    def select(cls, chunk, page_metas, dtype, list_nullable: bool, item_nullable: bool, selection, ctx=None,
+               large: bool = False, packed: bool = False):
+        """The decoder of the top-level rows `selection` names (a
+        pa_amd.SelectedListDecoder): pages without a selected row are not
+        planned or decoded.  A pa_amd.Selection has its page rows read from
+        the chunk on the device (packed must be False); a ResolvedSelection
+        was resolved against row metas PageMeta(length, rows), and with
+        packed=True `chunk` holds only the touched pages, back to back."""
+        from .select import SelectedListDecoder
+
+        return SelectedListDecoder(chunk, page_metas, dtype, list_nullable, item_nullable, selection, ctx, large, packed)
+
     def alloc_outputs(self):
         torch = self._torch
         dev = f"cuda:{self.ctx.device}"

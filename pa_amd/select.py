@@ -1,6 +1,8 @@
-"""Selective reads: decode only the selected rows of a flat column.
+"""Selective reads: decode only the selected rows of a flat column or of a
+List<primitive> column.
 
-A `Selection` is an LSB-first Arrow bitmap in HBM over a column's rows.  It
+A `Selection` is an LSB-first Arrow bitmap in HBM over a column's rows (a
+List column's top-level rows).  It
 is resolved against the column's page metas on the device (k_sel_count, one
 readback); pages without a selected row are then never uploaded, planned,
 staged or decoded.  The decoders here return exactly the selected rows, in
@@ -14,8 +16,22 @@ offsets that start at 0):
   read_selected                  one shot
   StrawboatFile.read_selected    from a file: uploads only the touched runs
 
-Nested leaves are out of scope (row selection there needs per-level
-compaction of the offsets): StrawboatError(E_NYI)."""
+List<T> / LargeList<T> over a fixed-width leaf: the result is the dense List
+array of the selected rows (offsets from 0, list validity, the rows' leaves
+back to back, leaf validity).  The footer's num_values of a nested page is
+its level count, so the selection is resolved against the page ROWS, each
+page's first u32, fetched first:
+
+  list_page_rows                 from a chunk in HBM    (sb_list_page_rows)
+  StrawboatFile.page_rows        from the file, 4 bytes a page (sb_file_page_rows)
+  ListColumnDecoder.select       sb_plan_selected_list_column + sb_decode_list_selected
+  read_selected_list             one shot
+  StrawboatFile.read_selected_list
+
+The selected leaf count is known only after the decode: the plan reports the
+touched pages' leaves as a bound (leaf_bound), outputs are allocated for
+that, written_leaves() is read back.  Deeper chains, Struct / Map and Utf8 /
+Boolean leaves under a list are out of scope: StrawboatError(E_NYI)."""
 from __future__ import annotations
 
 import ctypes
@@ -309,6 +325,128 @@ class SelectedBinaryDecoder(_SelectedBase):
         return o[: self.num_rows + 1], v[: self.written_bytes()], m
 
 
+def list_page_rows(chunk, page_metas: Sequence[PageMeta], ctx=None) -> List[int]:
+    """The top-level rows of every page of a nested column chunk in HBM (each
+    page's first u32: sb_list_page_rows, one small kernel and one readback).
+    The footer's num_values of such a page is its level count."""
+    ctx = resolve_context(ctx, chunk)
+    buf = _as_device_bytes(chunk, ctx.device)
+    n = len(page_metas)
+    metas = (N.PageMetaC * max(1, n))(*[N.PageMetaC(m.length, m.num_values) for m in page_metas])
+    rows = (ctypes.c_uint64 * max(1, n))()
+    st = N.lib().sb_list_page_rows(ctx._h, ctypes.c_void_p(buf.data_ptr()), buf.numel(), metas, n, rows)
+    if st:
+        raise _error(st, ctx.error())
+    return [int(rows[i]) for i in range(n)]
+
+
+class SelectedListDecoder(_SelectedBase):
+    """ListColumnDecoder.select: the selected top-level rows of a List<T> /
+    LargeList<T> column over a fixed-width leaf, as a dense List array.
+
+    num_rows: the selected rows; num_pages: the touched pages; leaf_bound:
+    the touched pages' leaves, which bounds the selected leaves (only the
+    decode learns their count: written_leaves()).  Outputs are allocated for
+    leaf_bound leaves."""
+
+    def __init__(self, chunk, page_metas, dtype, list_nullable: bool, item_nullable: bool, selection, ctx=None,
+                 large: bool = False, packed: bool = False):
+        import torch
+
+        from .nested import ListDescC, _lib as _list_lib
+
+        self._torch = torch
+        self.ctx = resolve_context(ctx, chunk)
+        phys = int(dtype) if isinstance(dtype, (int, np.integer)) else physical_type(np.dtype(dtype))
+        self.phys = phys
+        self.dtype = None if isinstance(dtype, (int, np.integer)) else np.dtype(dtype)
+        self.list_nullable, self.item_nullable = bool(list_nullable), bool(item_nullable)
+        self.offset_width = 8 if large else 4
+        self.chunk = _as_device_bytes(chunk, self.ctx.device)
+        self.metas = list(page_metas)
+        if isinstance(selection, ResolvedSelection):
+            self.resolved, self._own_resolved = selection, False
+        else:
+            if packed:
+                raise N.StrawboatError(N.E_ARG, "a packed chunk holds only the touched pages: resolve the selection "
+                                                "against the page rows first (PageMeta(length, rows))")
+            rows = list_page_rows(self.chunk, self.metas, self.ctx)
+            self.resolved = selection.resolve([PageMeta(m.length, r) for m, r in zip(self.metas, rows)], self.ctx)
+            self._own_resolved = True
+        self.selection = self.resolved.selection
+        L = _list_lib()
+        metas = (N.PageMetaC * max(1, len(self.metas)))(*[N.PageMetaC(m.length, m.num_values) for m in self.metas])
+        desc = ListDescC(phys, int(self.list_nullable), int(self.item_nullable), self.offset_width)
+        h = ctypes.c_void_p()
+        st = L.sb_plan_selected_list_column(self.ctx._h, ctypes.byref(desc), self.resolved._h, metas, len(self.metas),
+                                            ctypes.c_void_p(self.chunk.data_ptr()), self.chunk.numel(),
+                                            int(bool(packed)), ctypes.byref(h))
+        if st:
+            if self._own_resolved:
+                self.resolved.close()
+            raise _error(st, self.ctx.error())
+        self._h = h
+        self.num_rows = int(L.sb_plan_num_rows(h))
+        self.num_pages = int(L.sb_plan_num_pages(h))
+        self.leaf_bound = int(L.sb_plan_num_leaves(h))
+
+    def alloc_outputs(self):
+        torch = self._torch
+        dev = f"cuda:{self.ctx.device}"
+        odt = torch.int64 if self.offset_width == 8 else torch.int32
+        offsets = torch.zeros(self.num_rows + 1, dtype=odt, device=dev)
+        tdt = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[self.dtype.itemsize]
+        values = torch.empty(max(self.leaf_bound, 1), dtype=tdt, device=dev)
+        bm = lambda n: torch.zeros(max((n + 31) // 32, 1) * 4, dtype=torch.uint8, device=dev)  # noqa: E731
+        lv = bm(self.num_rows) if self.list_nullable else None
+        fv = bm(self.leaf_bound) if self.item_nullable else None
+        return offsets, lv, values, fv
+
+    def decode_async(self, offsets=None, list_validity=None, values=None, leaf_validity=None):
+        from .nested import ListOutC
+
+        if offsets is None:
+            offsets, list_validity, values, leaf_validity = self.alloc_outputs()
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        out = ListOutC(p(offsets), p(list_validity), p(values), p(leaf_validity))
+        st = N.lib().sb_decode_list_selected(self.ctx._h, self._h, ctypes.byref(out))
+        if st:
+            raise _error(st, self.ctx.error())
+        return offsets, list_validity, values, leaf_validity
+
+    def written_leaves(self) -> int:
+        """Leaves the last decode wrote (waits for it)."""
+        n = ctypes.c_uint64()
+        st = N.lib().sb_plan_selected_leaves(self.ctx._h, self._h, ctypes.byref(n))
+        if st:
+            raise _error(st, self.ctx.error())
+        return n.value
+
+    def decode(self, *outs):
+        """(offsets[:num_rows + 1], list validity | None, values narrowed to
+        the leaves written, leaf validity | None)."""
+        o, lv, v, fv = self.decode_async(*outs)
+        self.check()
+        return o[: self.num_rows + 1], lv, v[: self.written_leaves()], fv
+
+    def close(self):
+        super().close()
+        if getattr(self, "_own_resolved", False):
+            self.resolved.close()
+            self._own_resolved = False
+
+
+def read_selected_list(chunk, page_metas: Sequence[PageMeta], dtype, list_nullable: bool, item_nullable: bool,
+                       selection, ctx=None, large: bool = False, packed: bool = False):
+    """One shot: the selected rows of a List<T> column chunk ->
+    (offsets, list validity | None, values, leaf validity | None)."""
+    dec = SelectedListDecoder(chunk, page_metas, dtype, list_nullable, item_nullable, selection, ctx, large, packed)
+    try:
+        return dec.decode()
+    finally:
+        dec.close()
+
+
 def read_selected(chunk, page_metas: Sequence[PageMeta], dtype_or_physical_type, nullable: bool, selection,
                   ctx=None, packed: bool = False):
     """One shot: the selected rows of a flat column chunk.  A numpy dtype
@@ -354,5 +492,40 @@ def file_read_selected(f, col: int, selection: Selection, ctx=None):
         pt = leaf.physical_type
         what = pt if pt in _BINARY_TYPES else _DTYPE[pt]
         return read_selected(buf[:max(total, 1)], cm.pages, what, leaf.nullable, res, ctx, packed=True)
+    finally:
+        res.close()
+
+
+def file_read_selected_list(f, col: int, selection: Selection, ctx=None):
+    """StrawboatFile.read_selected_list: the page rows come from the file
+    (page_rows: one 4-byte read per page), the selection is resolved against
+    them, only the runs of touched pages are uploaded and decoded with
+    packed = 1."""
+    import torch
+
+    from .file import _DTYPE
+
+    if not 0 <= col < f.num_columns or len(f.leaves) != f.num_columns:
+        raise N.StrawboatError(N.E_ARG, f"column {col} out of range")
+    leaf = f.leaves[col]
+    if leaf.depth != 1 or leaf.flags or leaf.struct_mask or leaf.map_mask or leaf.physical_type not in _DTYPE \
+            or _DTYPE[leaf.physical_type] == np.bool_:
+        raise N.StrawboatError(N.E_NYI, f"leaf {leaf.name}: row selection takes one List / LargeList nest over a "
+                                        f"fixed-width leaf")
+    ctx = resolve_context(ctx, selection.bitmap)
+    cm = f.columns[col]
+    rows = f.page_rows(col)
+    res = selection.resolve([PageMeta(m.length, r) for m, r in zip(cm.pages, rows)], ctx)
+    try:
+        runs = res.runs()
+        total = sum(r[1] for r in runs)
+        buf = torch.empty(max(total, 1), dtype=torch.uint8, device=f"cuda:{ctx.device}")
+        pos = 0
+        for off, ln, _, _ in runs:
+            f._check(N.lib().sb_file_upload(ctx._h, f._h, cm.offset + off, ln, ctypes.c_void_p(buf.data_ptr() + pos)))
+            pos += ln
+        f.last_uploaded_bytes = total
+        return read_selected_list(buf[:max(total, 1)], cm.pages, _DTYPE[leaf.physical_type], leaf.list_nullable[0],
+                                  leaf.nullable, res, ctx, large=leaf.large_list[0], packed=True)
     finally:
         res.close()

@@ -88,6 +88,13 @@ extern "C" {
     pub fn sb_plan_selected_values_bytes(ctx: *mut sb_ctx, plan: *mut sb_plan, bytes: *mut u64) -> i32;
     pub fn sb_plan_selected_stats(plan: *const sb_plan, pages_direct: *mut u64, pages_compacted: *mut u64,
                                   scratch_bytes: *mut u64) -> i32;
+    pub fn sb_list_page_rows(ctx: *mut sb_ctx, d_chunk: *const u8, chunk_len: u64, metas: *const sb_page_meta,
+                             n_pages: u64, rows: *mut u64) -> i32;
+    pub fn sb_plan_selected_list_column(ctx: *mut sb_ctx, desc: *const sb_list_desc, sel: *const sb_select,
+                                        metas: *const sb_page_meta, n_pages: u64, d_chunk: *const u8,
+                                        chunk_len: u64, packed: i32, out: *mut *mut sb_plan) -> i32;
+    pub fn sb_decode_list_selected(ctx: *mut sb_ctx, plan: *mut sb_plan, out: *const sb_list_out) -> i32;
+    pub fn sb_plan_selected_leaves(ctx: *mut sb_ctx, plan: *mut sb_plan, leaves: *mut u64) -> i32;
     pub fn sb_plan_destroy(plan: *mut sb_plan);
     pub fn sb_plan_num_rows(plan: *const sb_plan) -> u64;
     pub fn sb_plan_values_bytes(plan: *const sb_plan) -> u64;
@@ -190,6 +197,7 @@ extern "C" {
     pub fn sb_file_column(f: *const sb_file, col: u64, offset: *mut u64, chunk_len: *mut u64, n_pages: *mut u64,
                           pages: *mut *const sb_page_meta) -> i32;
     pub fn sb_file_schema(f: *const sb_file, bytes: *mut *const u8, len: *mut u64) -> i32;
+    pub fn sb_file_page_rows(f: *mut sb_file, col: u64, rows: *mut u64, cap: u64) -> i32;
     pub fn sb_file_upload(ctx: *mut sb_ctx, f: *mut sb_file, offset: u64, len: u64, d_dst: *mut c_void) -> i32;
 }
 

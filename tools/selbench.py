@@ -1,16 +1,19 @@
 """Selective reads against what a caller does without them: a full decode
 (and, for Int32, values[mask] in torch).
 
-Columns: C2-shaped Int32 (8192-row pages, adaptive ratio 1.2) and C3-shaped
-nullable Utf8 (LZ4 pages).  Selections: all rows, one 1 % range not aligned
+Columns: C2-shaped Int32 (8192-row pages, adaptive ratio 1.2), C3-shaped
+nullable Utf8 (LZ4 pages) and C4-shaped List<Int32> (nullable lists of
+nullable items, lengths 0..2, adaptive ratio 1.2).  Selections: all rows, one 1 % range not aligned
 to pages, ten 0.1 % ranges, Bernoulli 10 % and 0.1 %.  Per (column,
 selection) the variants are timed with HIP events after a warm-up,
 alternating inside one loop, medians reported; the plan (resolve + page
-tables, with its readback) is timed on the host.  The file leg reads both
+tables, with its readback) is timed on the host.  The file leg reads the
 columns from a strawboat file: whole-chunk upload + full decode against
-StrawboatFile.read_selected, wall clock, with the bytes uploaded.
+StrawboatFile.read_selected / read_selected_list, wall clock, with the bytes
+uploaded; for the List column the share of page_rows (one 4-byte read per
+page before anything is uploaded) is reported on its own.
 
-python tools/selbench.py [--int-rows N] [--utf8-rows N] [--reps K] [--out FILE]"""
+python tools/selbench.py [--int-rows N] [--utf8-rows N] [--list-rows N] [--columns a,b] [--reps K] [--out FILE]"""
 import argparse
 import json
 import os
@@ -58,6 +61,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--int-rows", type=int, default=20 * 1024 * 1024)
     ap.add_argument("--utf8-rows", type=int, default=5_000_000)
+    ap.add_argument("--list-rows", type=int, default=5_000_000)
+    ap.add_argument("--columns", default="c2_int32,c3_utf8,c4_list", help="comma-separated subset of the columns")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "select_bench.json"))
     args = ap.parse_args()
@@ -69,21 +74,40 @@ def main():
 
     ctx = pa_amd.default_context(0)
     rng = np.random.default_rng(77)
-    x = bench.gen_c2(args.int_rows, 3, "mix")
-    ichunk, imetas = pa_amd.encode_column(x, None, False, pa_amd.WriteOptions(default_compress_ratio=1.2,
-                                                                              max_page_size=8192, seed=3))
-    svals, soffs = bench.decimal_strings(rng.integers(0, 10**6, args.utf8_rows))
-    svalid = rng.random(args.utf8_rows) >= 0.1
-    schunk, smetas = pa_amd.encode_binary_column(svals, soffs, svalid, True,
-                                                 pa_amd.WriteOptions(default_compression=1, max_page_size=8192, seed=1))
-    cols = [dict(name="c2_int32", chunk=ichunk, metas=imetas, rows=args.int_rows, binary=False),
-            dict(name="c3_utf8", chunk=schunk, metas=smetas, rows=args.utf8_rows, binary=True)]
+    want = args.columns.split(",")
+    cols = []
+    if "c2_int32" in want:
+        x = bench.gen_c2(args.int_rows, 3, "mix")
+        ichunk, imetas = pa_amd.encode_column(x, None, False, pa_amd.WriteOptions(default_compress_ratio=1.2,
+                                                                                  max_page_size=8192, seed=3))
+        cols.append(dict(name="c2_int32", chunk=ichunk, metas=imetas, rows=args.int_rows, kind="flat"))
+    if "c3_utf8" in want:
+        svals, soffs = bench.decimal_strings(rng.integers(0, 10**6, args.utf8_rows))
+        svalid = rng.random(args.utf8_rows) >= 0.1
+        schunk, smetas = pa_amd.encode_binary_column(svals, soffs, svalid, True,
+                                                     pa_amd.WriteOptions(default_compression=1, max_page_size=8192, seed=1))
+        cols.append(dict(name="c3_utf8", chunk=schunk, metas=smetas, rows=args.utf8_rows, kind="binary"))
+    if "c4_list" in want:  # bench.WorkloadC4's shape
+        lens = rng.integers(0, 3, args.list_rows)
+        lvalid = rng.random(args.list_rows) >= 0.1
+        lens[~lvalid] = 0
+        loffs = np.zeros(args.list_rows + 1, np.int64)
+        np.cumsum(lens, out=loffs[1:])
+        child = rng.integers(0, 1 << 16, int(loffs[-1])).astype(np.int32)
+        cvalid = rng.random(int(loffs[-1])) >= 0.2
+        lchunk, lmetas = pa_amd.encode_list_column(loffs, child, lvalid, cvalid, True, True,
+                                                   pa_amd.WriteOptions(default_compress_ratio=1.2, max_page_size=8192,
+                                                                       seed=4))
+        cols.append(dict(name="c4_list", chunk=lchunk, metas=lmetas, rows=args.list_rows, kind="list",
+                         leaves=int(loffs[-1])))
     records = []
     for col in cols:
         n = col["rows"]
         dchunk = torch.from_numpy(np.frombuffer(col["chunk"], np.uint8).copy()).cuda()
-        if col["binary"]:
+        if col["kind"] == "binary":
             full = pa_amd.BinaryColumnDecoder(dchunk, col["metas"], pa_amd.UTF8, True, ctx)
+        elif col["kind"] == "list":
+            full = pa_amd.ListColumnDecoder(dchunk, col["metas"], np.int32, True, True, ctx)
         else:
             full = pa_amd.ColumnDecoder(dchunk, col["metas"], np.int32, False, ctx)
         fout = full.alloc_outputs()
@@ -104,8 +128,10 @@ def main():
                     dec.close()
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                if col["binary"]:
+                if col["kind"] == "binary":
                     dec = pa_amd.BinaryColumnDecoder.select(dchunk, col["metas"], pa_amd.UTF8, True, sel, ctx)
+                elif col["kind"] == "list":  # (the page rows are read from the chunk inside the plan time)
+                    dec = pa_amd.ListColumnDecoder.select(dchunk, col["metas"], np.int32, True, True, sel, ctx)
                 else:
                     dec = pa_amd.ColumnDecoder.select(dchunk, col["metas"], np.int32, False, sel, ctx)
                 plan_ms.append((time.perf_counter() - t0) * 1e3)
@@ -113,7 +139,7 @@ def main():
             got = dec.decode(*sout)
             variants = {"full_decode": lambda: full.decode_async(*fout), "select": lambda: dec.decode_async(*sout)}
             ok = None
-            if not col["binary"]:
+            if col["kind"] == "flat":
                 variants["full_decode+mask"] = lambda: (full.decode_async(*fout), fout[0][:n][mask])
                 ok = bool(torch.equal(got[0], fout[0][:n][mask]))
             ms = timed(torch, variants, args.reps)
@@ -122,6 +148,8 @@ def main():
                        selection=sname, selected_rows=dec.num_rows, touched_pages=dec.num_pages, pages_direct=direct,
                        pages_compacted=compacted, scratch_bytes=scratch, plan_ms=float(np.median(plan_ms)), ms=ms,
                        matches_mask=ok)
+            if col["kind"] == "list":
+                rec.update(leaves=col["leaves"], leaf_bound=dec.leaf_bound, selected_leaves=dec.written_leaves())
             records.append(rec)
             print(json.dumps(rec), flush=True)
             dec.close()
@@ -134,7 +162,9 @@ def main():
     except ImportError:
         pa = None
     if pa is not None:
-        schema = pa.schema([pa.field("a", pa.int32(), False), pa.field("s", pa.utf8(), True)])
+        fields = {"c2_int32": pa.field("a", pa.int32(), False), "c3_utf8": pa.field("s", pa.utf8(), True),
+                  "c4_list": pa.field("l", pa.list_(pa.field("item", pa.int32(), True)), True)}
+        schema = pa.schema([fields[c["name"]] for c in cols])
         with tempfile.TemporaryDirectory() as d:
             path = os.path.join(d, "sel.sb")
             with open(path, "wb") as fh:
@@ -155,9 +185,16 @@ def main():
                             t["file_full"].append((time.perf_counter() - t0) * 1e3)
                             dec.close()
                             t0 = time.perf_counter()
-                            f.read_selected(c, sel, ctx)
+                            if col["kind"] == "list":
+                                f.read_selected_list(c, sel, ctx)
+                            else:
+                                f.read_selected(c, sel, ctx)
                             torch.cuda.synchronize()
                             t["file_select"].append((time.perf_counter() - t0) * 1e3)
+                            if col["kind"] == "list":  # its fixed cost per page, on its own
+                                t0 = time.perf_counter()
+                                f.page_rows(c)
+                                t.setdefault("page_rows", []).append((time.perf_counter() - t0) * 1e3)
                         rec = dict(column=col["name"], selection=sname, leg="file", chunk_bytes=len(col["chunk"]),
                                    uploaded_bytes=f.last_uploaded_bytes,
                                    wall_ms={k: float(np.median(v)) for k, v in t.items()})
