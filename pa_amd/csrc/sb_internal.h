@@ -133,7 +133,7 @@ int launch_patas(const InflateLaunch& a, void* stream);
 int launch_zinflate(const InflateLaunch& a, void* stream);
 constexpr uint32_t kInflateGrid = 2048;  // 4-wave workgroups: 8 waves per SIMD on 256 CUs
 
-// Launch entry points (sb_decode.hip).
+// Launch entry points (sb_decode.hip; launch_list and launch_nest: sb_list.hip).
 struct LaunchArgs {
   const uint8_t* chunk;
   const PageDesc* pages;
