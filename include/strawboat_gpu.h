@@ -69,6 +69,14 @@ typedef enum {
   SB_T_UTF8 = 13,         /* i32 offsets; values checked as Utf8Array::try_new does (OutOfSpec) */
   SB_T_LARGE_UTF8 = 14,   /* i64 offsets */
   SB_T_BOOLEAN = 15,      /* values are an LSB-first bitmap (read_boolean, read/array/boolean.rs:191-219) */
+  /* i128 / i256 pages (`impl IntegerType`, compression/integer/traits.rs:30-39), the storage of
+   * Decimal / Decimal256: 16- / 32-byte little-endian two's complement values, Arrow's decimal
+   * buffers.  Flat columns only: sb_plan_column, sb_plan_column_at, sb_decode_planned,
+   * sb_plan_status, sb_decode_column, sb_decompress_values, sb_encode_column and sb_encode_page
+   * take them (the values pointer 16-byte aligned on the device, else SB_E_ARG); every other
+   * entry point that takes a physical type answers SB_E_NYI. */
+  SB_T_INT128 = 16,
+  SB_T_INT256 = 17,
 } sb_physical_type;
 
 /* PageMeta (src/lib.rs:75-80): compressed page length and num_values. */
@@ -599,8 +607,11 @@ void sb_free(void* p);
 /* ---- file reader: footer, schema, file -> HBM staging ------------------- */
 /* One leaf of the schema in arrow2's to_leaves order (write/common.rs:68),
  * i.e. the order of the file's columns: its logical type (the IPC Schema.fbs
- * Type union tag), the reader's physical type (0 when no page path exists,
- * e.g. Decimal, Float16), and the nests above it -- the InitNested chain of
+ * Type union tag), the reader's physical type (0 when the logical type names
+ * none by itself: Float16 and the interval types have no page path, and a
+ * Decimal's pages are SB_T_INT128 / SB_T_INT256 by its decimal_bits -- a flat
+ * Decimal leaf is planned with that type, one under a nest is not decoded
+ * here), and the nests above it -- the InitNested chain of
  * deserialize_nested (read/deserialize.rs:202-230): List / LargeList / Map
  * (and FixedSizeList) nests and Struct nests, outermost first, each with a
  * schema-wide id (pre-order) so the leaves of one struct or map can be
@@ -624,6 +635,9 @@ typedef struct {
   uint32_t struct_mask;               /* bit d: nest d is a Struct */
   uint32_t map_mask;                  /* bit d: nest d is a Map (its child nest is the entries struct) */
   int32_t nest_id[SB_MAX_NEST];       /* per nest: the nest field's pre-order id in the schema */
+  int32_t decimal_bits;               /* Decimal.bitWidth (128 by default, or 256); 0 for every other leaf */
+  int32_t decimal_precision;          /* Decimal.precision */
+  int32_t decimal_scale;              /* Decimal.scale */
 } sb_leaf_info;
 
 /* infer_schema (read/reader.rs:227-241) + arrow2 deserialize_schema: the

@@ -1,6 +1,6 @@
 """pa_amd: MI355X-native page encode/decode engine for the strawboat format
 (drop-in for the codec path of b41sh/pa).  See DESIGN.md."""
-from ._native import StrawboatError, build, lib  # noqa: F401
+from ._native import INT128, INT256, StrawboatError, build, lib  # noqa: F401
 from .read import (  # noqa: F401
     ColumnDecoder,
     ColumnMeta,

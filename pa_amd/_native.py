@@ -19,6 +19,7 @@ OK, E_OUT_OF_SPEC, E_NYI, E_IO, E_CODEC, E_DEVICE, E_ARG = 0, 1, 2, 3, 4, 5, 6
 # sb_physical_type
 INT8, INT16, INT32, INT64, UINT8, UINT16, UINT32, UINT64, FLOAT32, FLOAT64 = range(1, 11)
 BOOLEAN = 15
+INT128, INT256 = 16, 17  # i128 / i256 pages: the storage of Decimal / Decimal256
 
 EXPORTED = [
     "sb_ctx_create", "sb_ctx_destroy", "sb_ctx_set_stream", "sb_ctx_stream", "sb_ctx_device", "sb_sync", "sb_last_error",
@@ -76,7 +77,9 @@ class LeafInfoC(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 64), ("arrow_type", ctypes.c_int32), ("physical_type", ctypes.c_int32),
                 ("nullable", ctypes.c_int32), ("depth", ctypes.c_int32), ("list_nullable", ctypes.c_int32 * MAX_NEST),
                 ("large_list", ctypes.c_int32 * MAX_NEST), ("flags", ctypes.c_uint32), ("top_field", ctypes.c_int32),
-                ("struct_mask", ctypes.c_uint32), ("map_mask", ctypes.c_uint32), ("nest_id", ctypes.c_int32 * MAX_NEST)]
+                ("struct_mask", ctypes.c_uint32), ("map_mask", ctypes.c_uint32), ("nest_id", ctypes.c_int32 * MAX_NEST),
+                ("decimal_bits", ctypes.c_int32), ("decimal_precision", ctypes.c_int32),
+                ("decimal_scale", ctypes.c_int32)]
 
 
 class PrimitiveOutC(ctypes.Structure):

@@ -158,6 +158,17 @@ static int type_width(int t, bool* is_float) {
   return 0;
 }
 
+// A flat column's plan also takes Int128 / Int256 (`impl IntegerType for i128 /
+// i256`, compression/integer/traits.rs:30-39).  Every other plan asks
+// type_width and refuses them (SB_E_NYI, naming the type).
+static int flat_width(int t, bool* is_float) {
+  if (t == SB_T_INT128 || t == SB_T_INT256) {
+    *is_float = false;
+    return t == SB_T_INT128 ? 16 : 32;
+  }
+  return type_width(t, is_float);
+}
+
 extern "C" {
 
 const char* sb_status_str(int st) {
@@ -406,7 +417,7 @@ static sb_status plan_pages(sb_ctx* ctx, const sb_column_desc* desc, const uint8
                             std::vector<sb::PageDesc> pages, sb_plan** out, int regions, const uint32_t* ids) {
   const uint64_t n_pages = pages.size();
   bool is_float;
-  int width = type_width(desc->physical_type, &is_float);
+  int width = flat_width(desc->physical_type, &is_float);
   const int ptype = desc->physical_type;
   const int owidth = (ptype == SB_T_BINARY || ptype == SB_T_UTF8) ? 4
                      : (ptype == SB_T_LARGE_BINARY || ptype == SB_T_LARGE_UTF8) ? 8 : 0;
@@ -731,6 +742,9 @@ sb_status sb_decode_planned(sb_ctx* ctx, sb_plan* p, const sb_primitive_out* out
   if (p->binary) return fail(ctx, SB_E_ARG, "binary plan: use sb_decode_binary_planned");
   if (p->n_rows && !out->d_values) return fail(ctx, SB_E_ARG, "values buffer is null");
   if (p->desc.nullable && p->n_rows && !out->d_validity) return fail(ctx, SB_E_ARG, "validity buffer is null");
+  // 16- / 32-byte values leave as 16-byte vector stores at row_off * W from the base
+  if (p->width >= 16 && ((uintptr_t)out->d_values & 15))
+    return fail(ctx, SB_E_ARG, "values buffer of a %d-byte column is not 16-byte aligned", p->width);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (p->desc.nullable && p->validity_needs_zero)
     HIP_TRY(ctx, hipMemsetAsync(out->d_validity, 0, (p->n_rows + 31) / 32 * 4, ctx->stream));

@@ -332,6 +332,62 @@ __device__ __forceinline__ void run_leaf(const Src& s, Shared& sh, const Stream 
   }
 }
 
+// The same driver for a leaf stream of 16- or 32-byte values (Int128 /
+// Int256: `impl IntegerType for i128 / i256`, integer/traits.rs:30-39).  One
+// value per lane per step, fn(index, v): a quad of 32-byte values would be 32
+// VGPRs of payload.  Bitpacking and DeltaBitpacking never hold such values
+// (their ratio is 0 unless size_of::<T>() == 4, bp.rs:92-100,
+// delta_bp.rs:97-105; decoding one writes u32s into a Vec<T> and sets its
+// length over bytes it never wrote, bp.rs:67-86): OutOfSpec, as Patas is.
+template <int SW, class Src, class Fn>
+__device__ __forceinline__ void run_leaf_wide(const Src& s, Shared& sh, const Stream st, Fn&& fn) {
+  static_assert(SW == 16 || SW == 32, "wide values only");
+  const uint32_t tid = threadIdx.x;
+  switch (st.codec) {
+    case 0: {  // None (basic.rs:68-71)
+      if ((uint64_t)st.csize != (uint64_t)st.n * SW) { if (tid == 0) set_err(sh, ST_OUT_OF_SPEC); return; }
+      for (uint32_t i = tid; i < st.n; i += NT) fn(i, ldv<SW>(s, st.body + i * SW));
+      return;
+    }
+    case 12: {  // OneValue (one_value.rs:77-94)
+      if (st.csize < SW) { if (tid == 0) set_err(sh, ST_IO); return; }
+      const auto x = ldv<SW>(s, st.body);
+      for (uint32_t i = tid; i < st.n; i += NT) fn(i, x);
+      return;
+    }
+    case 10: {  // RLE: [u32 count][T value] runs (rle.rs:106-134)
+      rle_prepare<SW>(s, sh, st);
+      if (sh.err) return;
+      const uint32_t runsz = 4 + SW;
+      if (st.n <= kRleFastRows && !(sh.rle_flags & 4)) {
+        for (uint32_t i = tid; i < st.n; i += NT) {
+          const uint32_t b = i & 31;
+          const uint32_t m = b == 31 ? 0xFFFFFFFFu : ((2u << b) - 1);
+          const uint32_t r = sh.rle_pref[i >> 5] + __popc(sh.rle_bits[i >> 5] & m) - 1;
+          fn(i, ldv<SW>(s, st.body + r * runsz + 4));
+        }
+        return;
+      }
+      for (uint32_t i = tid; i < st.n; i += NT) {
+        uint32_t rs, re;
+        const uint32_t r = rle_find<SW>(s, sh, st, i, &rs, &re);
+        fn(i, ldv<SW>(s, st.body + r * runsz + 4));
+      }
+      return;
+    }
+    case 1:
+    case 2:
+    case 3:   // expanded first by the deferred / inflate passes, never a leaf here
+    case 11:
+    case 13:
+      if (tid == 0) set_err(sh, ST_NYI);
+      return;
+    default:  // 14 / 15 / 16 included
+      if (tid == 0) set_err(sh, ST_OUT_OF_SPEC);
+      return;
+  }
+}
+
 // Parse a nested [codec][csize][usize] header at p (bounded by end).
 template <class Src>
 __device__ __forceinline__ bool parse_stream(const Src& s, uint32_t p, uint32_t end, uint32_t n, Stream* st) {
@@ -1945,6 +2001,83 @@ __device__ __forceinline__ void decode_values(const Src& s, const LSrc& ls, Shar
   }
 }
 
+// decode_values for 16- and 32-byte values.  Each value leaves as one
+// (W = 16) or two 16-byte vector stores: the column base is 16-byte aligned
+// (sb_decode_planned refuses any other) and a page's base is row_off * W on
+// from it.  A leaf stream hands out one value per lane, so a wave's store
+// instruction covers 1 KiB (W = 16) of consecutive column bytes; a Dict index
+// stream keeps run_leaf<4>'s quads and each lane gathers its four entries in
+// turn.  Dictionary entries and the Freq top value sit at any byte offset of
+// the page: ldv<W> reads dwords and realigns them.
+template <int W, class Src, class LSrc>
+__device__ __forceinline__ void decode_values_wide(const Src& s, const LSrc& ls, Shared& sh, const PageDesc& pd,
+                                                   const LaunchArgs& a) {
+  using T = typename VT<W>::T;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t n = pd.num_values;
+  uint8_t* obase = a.out_values + pd.row_off * W;
+  auto put = [&](uint32_t row, const T& v) {
+    u32x4* p = (u32x4*)(obase + (size_t)row * W);
+#pragma unroll
+    for (int h = 0; h < W / 16; h++) st_out(p + h, u32x4{v.d[4 * h], v.d[4 * h + 1], v.d[4 * h + 2], v.d[4 * h + 3]});
+  };
+  const uint32_t chain = sh.chain;
+  const Stream leaf = sh.sub;
+  const uint32_t k = sh.dict_k, doff = sh.dict_off;
+  // entry idx of the plain dictionary (k entries of W bytes, bounded by parse_dict)
+  auto entry = [&](uint32_t idx, bool* bad) {
+    T v{};
+    if (idx < k) v = ldv<W>(s, doff + idx * W);
+    else *bad = true;  // data[i] out of range panics
+    return v;
+  };
+
+  if (chain == CH_LEAF) {
+    run_leaf_wide<W>(ls, sh, leaf, put);
+    return;
+  }
+  if (chain == CH_DICT) {
+    run_leaf<4>(ls, sh, leaf, [&](uint32_t row, const uint32_t* idx, uint32_t nv) {
+      bool bad = false;
+#pragma unroll 1
+      for (uint32_t l = 0; l < nv; l++) put(row + l, entry(idx[l], &bad));
+      if (bad) set_err(sh, ST_OUT_OF_SPEC);
+    });
+    return;
+  }
+  if (sh.roar_pending) {
+    uint32_t cap;
+    uint8_t* tabs = region_roar(a, pd, &cap);
+    roaring_build(s, sh, tabs, cap);
+    if (sh.err) return;
+  }
+  T fill{};
+  if (chain == CH_DICT_FREQ) {
+    const uint32_t ti = (uint32_t)sh.freq_top;
+    if (ti >= k && leaf.n < n) { if (tid == 0) set_err(sh, ST_OUT_OF_SPEC); return; }
+    if (ti < k) fill = ldv<W>(s, doff + ti * W);
+  } else {
+    fill = ldv<W>(s, (uint32_t)sh.freq_top);  // (the top value's position in the page: decode_page)
+  }
+  for (uint32_t row = tid; row < n; row += NT) put(row, fill);
+  __syncthreads();  // the scatter below overwrites rows of the fill
+  auto scatter = [&](uint32_t i, const T& x) {
+    const uint32_t row = roaring_select(s, sh, i);
+    if (row < n) put(row, x);
+    else set_err(sh, ST_OUT_OF_SPEC);  // output[begin + val] out of range panics
+  };
+  if (chain == CH_FREQ) {
+    run_leaf_wide<W>(ls, sh, leaf, scatter);
+  } else {
+    run_leaf<4>(ls, sh, leaf, [&](uint32_t i0, const uint32_t* idx, uint32_t nv) {
+      bool bad = false;
+#pragma unroll 1
+      for (uint32_t l = 0; l < nv; l++) scatter(i0 + l, entry(idx[l], &bad));
+      if (bad) set_err(sh, ST_OUT_OF_SPEC);
+    });
+  }
+}
+
 __device__ __forceinline__ bool general_codec(uint32_t c) { return c == 1 || c == 2 || c == 3 || c == 16; }
 
 // MODE 0: main pass (general-codec / Patas leaves are deferred to a work
@@ -1985,6 +2118,7 @@ __device__ __forceinline__ void decode_page(const Src& s, Shared& sh, const Page
         }
       } else if (st.codec == 13) {
         if (!parse_freq(s, sh, st, W, &inner)) break;
+        if (W >= 16) sh.freq_top = st.body;  // wide: where the top value is (decode_values_wide loads it)
         chain = CH_FREQ;
         if (inner.codec == 11) {
           Stream ix;
@@ -1998,6 +2132,10 @@ __device__ __forceinline__ void decode_page(const Src& s, Shared& sh, const Page
       if (inner.codec == 11 || inner.codec == 13) { set_err(sh, ST_OUT_OF_SPEC); break; }
       if (FLT && (inner.codec == 14 || inner.codec == 15) && (chain == CH_LEAF || chain == CH_FREQ)) {
         set_err(sh, ST_OUT_OF_SPEC);  // no Bitpacking in decompress_double
+        break;
+      }
+      if (W >= 16 && inner.codec >= 14 && inner.codec <= 16 && (chain == CH_LEAF || chain == CH_FREQ)) {
+        set_err(sh, ST_OUT_OF_SPEC);  // no writer packs 16- / 32-byte values (run_leaf_wide)
         break;
       }
       sh.top = st;
@@ -2061,9 +2199,10 @@ __device__ __forceinline__ void decode_page(const Src& s, Shared& sh, const Page
       if constexpr (std::is_same<Src, LdsSrc>::value) {
         if (lf.codec == 16) {  // Patas: every thread of the workgroup
           const lds_u8* in = (const lds_u8*)((const uint8_t*)s.w + s.base + lf.body);
-          uint32_t st;
-          if (!FLT || idx_stream) st = ST_OUT_OF_SPEC;  // Patas only in decompress_double
-          else st = patas_expand<W>(in, lf.csize, (lds_u8*)xbuf, lf.n, sh);
+          uint32_t st = ST_OUT_OF_SPEC;  // Patas only in decompress_double
+          if constexpr (FLT && W <= 8) {
+            if (!idx_stream) st = patas_expand<W>(in, lf.csize, (lds_u8*)xbuf, lf.n, sh);
+          }
           if (st && tid == 0) set_err(sh, st);
         } else if (tid < 64) {
           lds_u8* xo = (lds_u8*)xbuf;
@@ -2085,8 +2224,13 @@ __device__ __forceinline__ void decode_page(const Src& s, Shared& sh, const Page
     }
   }
 
-  if constexpr (MODE == 2) decode_values<W>(s, *lsrc, sh, pd, a);
-  else decode_values<W>(s, s, sh, pd, a);
+  if constexpr (W >= 16) {
+    if constexpr (MODE == 2) decode_values_wide<W>(s, *lsrc, sh, pd, a);
+    else decode_values_wide<W>(s, s, sh, pd, a);
+  } else {
+    if constexpr (MODE == 2) decode_values<W>(s, *lsrc, sh, pd, a);
+    else decode_values<W>(s, s, sh, pd, a);
+  }
 }
 
 // Stage [pg, pg + len) into LDS with aligned 16-byte pieces.
@@ -2164,6 +2308,7 @@ __device__ __forceinline__ uint32_t wave_slot(uint32_t* ctr, bool want, uint32_t
 // reads the validity prefix and the stream header from HBM (the checks of
 // decode_page), appends the k_inflate job and tags the page; the staged /
 // global passes then only copy its validity bits.
+#ifndef SB_DECODE_WIDE  // (the run-time-width kernels live in the default object alone)
 __global__ __launch_bounds__(NT) void k_fix_light(LaunchArgs a, uint32_t n_pages, uint32_t W, uint32_t flt,
                                                    uint32_t* light) {
   for (uint32_t page = blockIdx.x * NT + threadIdx.x; page < n_pages; page += gridDim.x * NT) {
@@ -2188,6 +2333,7 @@ __global__ __launch_bounds__(NT) void k_fix_light(LaunchArgs a, uint32_t n_pages
     light[page] = lt ? 1 + vb : 0u;
   }
 }
+#endif
 
 // A header-only page in the staged / global passes: its validity bits only.
 __device__ __forceinline__ bool light_page(const LaunchArgs& a, const PageDesc& pd, uint32_t page) {
@@ -2347,6 +2493,7 @@ __device__ uint32_t fix_cascade(const GlbSrc& s, uint32_t len, uint32_t W, int n
   return bits;
 }
 
+#ifndef SB_DECODE_WIDE
 // The cascade bits of each listed page (fix_cascade), one thread per page.
 __global__ __launch_bounds__(NT) void k_fix_probe(const uint8_t* chunk, const PageDesc* pages, const uint32_t* list,
                                                   uint32_t n_list, uint32_t W, int nullable, uint32_t* probe) {
@@ -2371,6 +2518,7 @@ __global__ __launch_bounds__(NT) void k_zstd_scan(const uint8_t* chunk, const Pa
   const uint32_t f = (__ballot(c & 8) ? 1u : 0u) | (__ballot(c & 16) ? 2u : 0u) | (__ballot(c & 32) ? 4u : 0u);
   if (f && (threadIdx.x & 63) == 0) atomicOr(flag, f);
 }
+#endif
 
 template <int W, bool FLT>
 static int launch(int kind, const LaunchArgs& a, hipStream_t stream) {
@@ -2400,6 +2548,20 @@ static int launch(int kind, const LaunchArgs& a, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+#ifdef SB_DECODE_WIDE
+// This object holds the W = 16 / 32 instantiations of the page kernels and
+// nothing else: the same source compiled a second time, beside the default
+// object, so the build's critical path stays one compile of this file.
+}  // namespace sbk
+namespace sb {
+int launch_decode_wide(int width, int kind, const LaunchArgs& a, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (width == 16) return sbk::launch<16, false>(kind, a, s);
+  if (width == 32) return sbk::launch<32, false>(kind, a, s);
+  return -1;
+}
+}  // namespace sb
+#else
 // General-codec streams expanded straight into HBM, one wave per stream, each
 // wave with its own kRing-byte LDS history ring: 4 waves x 4 KiB per
 // workgroup, so 8 waves per SIMD can be resident and the serial token streams
@@ -4332,6 +4494,8 @@ int launch_decode_fixed(int width, bool is_float, int kind, const LaunchArgs& a,
     case 2: return sbk::launch<2, false>(kind, a, s);
     case 4: return sbk::launch<4, false>(kind, a, s);
     case 8: return sbk::launch<8, false>(kind, a, s);
+    case 16:
+    case 32: return launch_decode_wide(width, kind, a, stream);  // (the second object of this source)
   }
   return -2;
 }
@@ -4498,3 +4662,4 @@ int launch_bool(const LaunchArgs& a, void* stream) {
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 }  // namespace sb
+#endif  // SB_DECODE_WIDE

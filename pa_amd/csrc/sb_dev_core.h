@@ -37,6 +37,19 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 template <int W> struct VT { using T = uint32_t; };
 template <> struct VT<8> { using T = uint64_t; };
+// Int128 / Int256 (the storage of Decimal / Decimal256): L little-endian dwords
+template <int L>
+struct WideV {
+  uint32_t d[L];
+  __device__ __forceinline__ bool operator==(const WideV& o) const {
+    bool e = true;
+#pragma unroll
+    for (int k = 0; k < L; k++) e &= d[k] == o.d[k];
+    return e;
+  }
+};
+template <> struct VT<16> { using T = WideV<4>; };
+template <> struct VT<32> { using T = WideV<8>; };
 
 // ---------------------------------------------------------------------------
 // byte sources
@@ -62,6 +75,17 @@ struct LdsSrc {
     uint32_t a = w[i], b = w[i + 1], c = w[i + 2];
     return (uint64_t)__builtin_amdgcn_alignbyte(b, a, sh) |
            ((uint64_t)__builtin_amdgcn_alignbyte(c, b, sh) << 32);
+  }
+  // L dwords at any byte position (one dword of over-read, inside the pad)
+  template <int L>
+  __device__ __forceinline__ void words(uint32_t p, uint32_t* o) const {
+    p += base;
+    uint32_t i = p >> 2, sh = p & 3;
+    uint32_t d[L + 1];
+#pragma unroll
+    for (int k = 0; k <= L; k++) d[k] = w[i + k];
+#pragma unroll
+    for (int k = 0; k < L; k++) o[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh);
   }
   // the 4 lane words at p and (if need_hi) the 4 at p + 16, unaligned
   __device__ __forceinline__ void quad_words(uint32_t p, bool need_hi, uint32_t* d8) const {
@@ -97,6 +121,23 @@ struct GlbSrc {
   __device__ __forceinline__ uint64_t u64(uint32_t i) const {
     return (uint64_t)u32(i) | ((uint64_t)u32(i + 4) << 32);
   }
+  // L dwords at any byte position, from the aligned dwords that hold them
+  template <int L>
+  __device__ __forceinline__ void words(uint32_t i, uint32_t* o) const {
+    const uintptr_t a = (uintptr_t)(p + i);
+    g32* q = (g32*)(a & ~(uintptr_t)3);
+    const uint32_t sh = (uint32_t)(a & 3);
+    if (sh == 0) {
+#pragma unroll
+      for (int k = 0; k < L; k++) o[k] = q[k];
+      return;
+    }
+    uint32_t d[L + 1];
+#pragma unroll
+    for (int k = 0; k <= L; k++) d[k] = q[k];
+#pragma unroll
+    for (int k = 0; k < L; k++) o[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh);
+  }
   __device__ __forceinline__ void quad_words(uint32_t pos, bool need_hi, uint32_t* d8) const {
 #pragma unroll
     for (int k = 0; k < 4; k++) d8[k] = u32(pos + 4 * k);
@@ -112,7 +153,11 @@ struct GlbSrc {
 
 template <int W, class Src>
 __device__ __forceinline__ typename VT<W>::T ldv(const Src& s, uint32_t p) {
-  if constexpr (W == 8) return s.u64(p);
+  if constexpr (W >= 16) {
+    typename VT<W>::T v;
+    s.template words<W / 4>(p, v.d);
+    return v;
+  } else if constexpr (W == 8) return s.u64(p);
   else if constexpr (W == 4) return s.u32(p);
   else if constexpr (W == 2) return s.u32(p) & 0xFFFFu;
   else return s.u8(p);

@@ -91,25 +91,65 @@ struct Tr {
   }
 };
 
+// ---- i128 / i256 (`impl IntegerType`, integer/traits.rs:30-39): L little-endian
+// 64-bit limbs.  Equality and the hash cover every byte; the order key is the
+// value with its sign bit flipped, compared from the top limb down (the
+// signed order of i128's / i256's PartialOrd); as_i64 keeps the low 64 bits.
+template <int L>
+struct Wide {
+  uint64_t w[L];
+  bool operator==(const Wide& o) const {
+    for (int k = 0; k < L; k++)
+      if (w[k] != o.w[k]) return false;
+    return true;
+  }
+  bool operator!=(const Wide& o) const { return !(*this == o); }
+  bool operator<(const Wide& o) const {  // unsigned, top limb first
+    for (int k = L - 1; k >= 0; k--)
+      if (w[k] != o.w[k]) return w[k] < o.w[k];
+    return false;
+  }
+  bool operator>(const Wide& o) const { return o < *this; }
+};
+template <int L>
+struct Tr<Wide<L>> {
+  static constexpr bool kFloat = false;
+  static Wide<L> bits(const Wide<L>& v) { return v; }
+  static Wide<L> key(Wide<L> v) {
+    v.w[L - 1] ^= 0x8000000000000000ull;
+    return v;
+  }
+  static int64_t as_i64(const Wide<L>& v) { return (int64_t)v.w[0]; }  // `as i64`: truncates
+};
+
+static uint64_t hash_key(uint64_t k) { return k * 0x9E3779B97F4A7C15ull; }
+template <int L>
+static uint64_t hash_key(const Wide<L>& k) {
+  uint64_t h = 0;
+  for (int i = 0; i < L; i++) h = (h ^ k.w[i]) * 0x9E3779B97F4A7C15ull + (h >> 29);
+  return h;
+}
+
 // ---- open-addressing count table (gen_stats's distinct_values HashMap)
-struct CountMap {
-  std::vector<uint64_t> keys;
+template <class K>
+struct CountMapT {
+  std::vector<K> keys;
   std::vector<uint32_t> count, first;
   std::vector<uint8_t> used;
   size_t mask = 0, size = 0;
-  explicit CountMap(size_t n) {
+  explicit CountMapT(size_t n) {
     size_t cap = 16;
     while (cap < 2 * n + 16) cap <<= 1;
     keys.resize(cap); count.resize(cap); first.resize(cap); used.assign(cap, 0);
     mask = cap - 1;
   }
-  size_t slot(uint64_t k) const {
-    size_t i = (size_t)((k * 0x9E3779B97F4A7C15ull) >> 17) & mask;
+  size_t slot(const K& k) const {
+    size_t i = (size_t)(hash_key(k) >> 17) & mask;
     while (used[i] && keys[i] != k) i = (i + 1) & mask;
     return i;
   }
   // returns true if inserted
-  bool add(uint64_t k, uint32_t idx, size_t* where = nullptr) {
+  bool add(const K& k, uint32_t idx, size_t* where = nullptr) {
     size_t i = slot(k);
     bool ins = !used[i];
     if (ins) { used[i] = 1; keys[i] = k; count[i] = 0; first[i] = idx; size++; }
@@ -119,12 +159,14 @@ struct CountMap {
   }
 };
 
+using CountMap = CountMapT<uint64_t>;
+
 template <class T>
 struct Stats {
   size_t tuple_count = 0, total_bytes = 0, null_count = 0, unique_count = 0;
   bool is_sorted = true;
   T min{}, max{};
-  CountMap distinct;
+  CountMapT<decltype(Tr<T>::key(T{}))> distinct;
   explicit Stats(size_t n) : distinct(n) {}
 };
 
@@ -146,7 +188,7 @@ static void gen_stats(const Arr<T>& a, Stats<T>& s) {
   bool init = false;
   for (size_t i = 0; i < a.n; i++) {
     const T v = a.v[i];
-    const uint64_t kv = Tr<T>::key(v);
+    const auto kv = Tr<T>::key(v);
     if (bit(a.valid, i)) {
       if (kv < Tr<T>::key(last)) s.is_sorted = false;
       if (Tr<T>::key(last) != kv) last = v;
@@ -353,7 +395,7 @@ static void bp_encode(const Arr<T>& a, Bytes& o, bool delta) {  // bp.rs:37-65, 
 
 template <class T>
 static int dict_encode(const Arr<T>& a, const Opts& opt, Rng& rng, Bytes& o) {  // dict.rs:34-73
-  CountMap ids(a.n);
+  CountMapT<decltype(Tr<T>::bits(T{}))> ids(a.n);
   std::vector<uint32_t> idx(a.n), slot_id(ids.mask + 1);
   std::vector<T> sets;
   for (size_t i = 0; i < a.n; i++) {
@@ -384,7 +426,7 @@ static int freq_encode(const Arr<T>& a, const Stats<T>& st, const Opts& opt, Rng
     top_count(st, &first);
     top = a.v[first];
   }
-  const uint64_t tk = Tr<T>::key(top);
+  const auto tk = Tr<T>::key(top);
   std::vector<uint32_t> pos;
   std::vector<T> exc;
   for (size_t i = 0; i < a.n; i++) {
@@ -621,6 +663,8 @@ int encode_page(int phys, const void* values, const uint8_t* valid, size_t n, bo
     case SB_T_UINT64: return encode_page_t<uint64_t>(values, valid, n, nullable, false, opt, seed, out);
     case SB_T_FLOAT32: return encode_page_t<float>(values, valid, n, nullable, false, opt, seed, out);
     case SB_T_FLOAT64: return encode_page_t<double>(values, valid, n, nullable, false, opt, seed, out);
+    case SB_T_INT128: return encode_page_t<Wide<2>>(values, valid, n, nullable, true, opt, seed, out);
+    case SB_T_INT256: return encode_page_t<Wide<4>>(values, valid, n, nullable, true, opt, seed, out);
   }
   return SB_E_NYI;
 }
@@ -666,7 +710,7 @@ int encode_list_page(int phys, const int64_t* offsets, const uint8_t* list_valid
                      const void* child, const uint8_t* child_valid, bool item_nullable, const Opts& opt,
                      uint64_t seed, Bytes& out, uint64_t* num_levels) {
   const int ts = type_size(phys);
-  if (!ts) return SB_E_NYI;
+  if (!ts || ts > 8) return SB_E_NYI;  // (Int128 / Int256 leaves under a nest: not written here)
   Rng rng{seed};
   const uint32_t nl = list_nullable, ni = item_nullable, max_def = nl + 1 + ni;
   std::vector<uint32_t> rep, def;
@@ -908,6 +952,8 @@ int type_size(int phys) {
     case SB_T_INT16: case SB_T_UINT16: return 2;
     case SB_T_INT32: case SB_T_UINT32: case SB_T_FLOAT32: return 4;
     case SB_T_INT64: case SB_T_UINT64: case SB_T_FLOAT64: return 8;
+    case SB_T_INT128: return 16;
+    case SB_T_INT256: return 32;
   }
   return 0;
 }

@@ -2722,6 +2722,9 @@ extern "C" sb_status sb_encode_nested_column_device(sb_ctx* ctx, const sb_nested
   const int depth = desc->depth, phys = desc->physical_type;
   if (depth < 1 || depth > SB_MAX_NEST) return SB_E_NYI;
   const bool binary = sb::enc_type(phys).offset_width != 0;
+  if (phys == SB_T_INT128 || phys == SB_T_INT256)
+    return (sb_status)sb::ctx_fail(ctx, SB_E_NYI, phys == SB_T_INT128 ? "device nested encoder: physical type 16 (Int128)"
+                                                                       : "device nested encoder: physical type 17 (Int256)", 0);
   if (!sb::enc_type(phys).supported()) return SB_E_NYI;
   for (int d = 0; d < depth; d++) {
     if (!((desc->struct_mask >> d) & 1) && !d_nests[d].d_offsets) return SB_E_ARG;

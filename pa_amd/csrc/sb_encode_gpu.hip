@@ -251,6 +251,9 @@ extern "C" sb_status sb_encode_column_device(sb_ctx* ctx, int32_t physical_type,
                                              uint64_t out_capacity, uint64_t* out_len, sb_page_meta* h_metas,
                                              uint64_t metas_cap, uint64_t* n_pages) {
   if (!ctx || !opts || !out_len || !n_pages) return SB_E_ARG;
+  if (physical_type == SB_T_INT128 || physical_type == SB_T_INT256)  // (the host encoder writes them: sb_encode_column)
+    return (sb_status)sb::ctx_fail(ctx, SB_E_NYI, physical_type == SB_T_INT128 ? "device encoder: physical type 16 (Int128)"
+                                                                                : "device encoder: physical type 17 (Int256)", 0);
   const bool is_bool = physical_type == SB_T_BOOLEAN;  // d_values = the column's LSB bitmap
   const uint32_t w = sb::enc_type(physical_type).width;
   if (!w || (nullable && !d_validity) || (n_rows && (!d_values || !d_out))) return SB_E_ARG;
@@ -323,6 +326,9 @@ extern "C" sb_status sb_encode_list_column_device(sb_ctx* ctx, int32_t physical_
                                                   uint64_t out_capacity, uint64_t* out_len, sb_page_meta* h_metas,
                                                   uint64_t metas_cap, uint64_t* n_pages) {
   if (!ctx || !opts || !out_len || !n_pages || !d_offsets) return SB_E_ARG;
+  if (ctx && (physical_type == SB_T_INT128 || physical_type == SB_T_INT256))
+    return (sb_status)sb::ctx_fail(ctx, SB_E_NYI, physical_type == SB_T_INT128 ? "device list encoder: physical type 16 (Int128)"
+                                                                                : "device list encoder: physical type 17 (Int256)", 0);
   if (!sb::enc_type(physical_type).value_width()) return SB_E_NYI;
   if ((list_nullable && !d_list_validity) || (item_nullable && !d_child_validity) || (n_rows && !d_out))
     return SB_E_ARG;

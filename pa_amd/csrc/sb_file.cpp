@@ -191,6 +191,11 @@ struct Walk {
     li.physical_type = leaf_physical(fb, tag, ty);
     li.nullable = nullable;
     li.top_field = top;
+    if (tag == kDecimal) {  // Schema.fbs Decimal { precision: int; scale: int; bitWidth: int = 128; }
+      li.decimal_precision = ty ? fb.scalar<int32_t>(ty, 0, 0) : 0;
+      li.decimal_scale = ty ? fb.scalar<int32_t>(ty, 1, 0) : 0;
+      li.decimal_bits = ty ? fb.scalar<int32_t>(ty, 2, 128) : 128;
+    }
     if (path.depth > SB_MAX_NEST) li.flags |= SB_LEAF_TOO_DEEP;
     out.push_back(li);
   }

@@ -160,6 +160,9 @@ struct LaunchArgs {
 // kind: 0 = LDS-staged pages, 1 = pages read from HBM, 2 = deferred work list,
 // 3 = spilled work list (a.n_list = its upper bound)
 int launch_decode_fixed(int width, bool is_float, int kind, const LaunchArgs& a, void* stream);
+// The same for 16- / 32-byte values (Int128 / Int256): the instantiations of
+// sb_decode.hip's second object (-DSB_DECODE_WIDE).
+int launch_decode_wide(int width, int kind, const LaunchArgs& a, void* stream);
 // Plan time: per listed page (one thread each, from HBM) the cascade bits
 // probe[i] = 1 (a Freq in the cascade) | 2 (a general-codec / Patas leaf) |
 // 4 (under a Dict / Freq).

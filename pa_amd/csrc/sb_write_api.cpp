@@ -212,7 +212,7 @@ sb_status sb_encode_list_column(int32_t phys, const int64_t* h_offsets, const ui
                                 sb_page_meta** h_metas, uint64_t* n_pages) {
   if (!h_out || !out_len || !h_metas || !n_pages || !h_offsets || (n_rows && h_offsets[n_rows] > h_offsets[0] && !h_child))
     return SB_E_ARG;
-  if (!sb::enc::type_size(phys)) return SB_E_NYI;
+  if (!sb::enc::type_size(phys) || sb::enc::type_size(phys) > 8) return SB_E_NYI;  // (no Int128 / Int256 under a nest)
   if (list_nullable && h_list_validity) {  // a null slot emits one level and no leaf slot: it must be empty
     uint32_t dead = 0;
     for (uint64_t i = 0; i < n_rows; i++)
@@ -286,7 +286,7 @@ sb_status sb_encode_nested_column(const sb_nested_desc* desc, const sb_nest_in* 
   const int depth = desc->depth, phys = desc->physical_type;
   if (depth < 1 || depth > SB_MAX_NEST) return SB_E_NYI;
   const bool binary = phys >= SB_T_BINARY && phys <= SB_T_LARGE_UTF8;
-  if (!binary && phys != SB_T_BOOLEAN && !sb::enc::type_size(phys)) return SB_E_NYI;
+  if (!binary && phys != SB_T_BOOLEAN && (!sb::enc::type_size(phys) || sb::enc::type_size(phys) > 8)) return SB_E_NYI;
   sb::enc::NestLevel nests[SB_MAX_NEST];
   uint64_t count = n_rows;  // entries of the current nest
   for (int d = 0; d < depth; d++) {

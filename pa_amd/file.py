@@ -43,6 +43,18 @@ class Leaf:
     struct_mask: int = 0
     map_mask: int = 0
     nest_id: List[int] = field(default_factory=list)
+    decimal_bits: int = 0       # Schema.fbs Decimal.bitWidth (128 / 256); 0 for every other leaf
+    decimal_precision: int = 0
+    decimal_scale: int = 0
+
+    @property
+    def page_type(self) -> int:
+        """The physical type of the leaf's pages: physical_type, or for a
+        Decimal leaf (physical_type 0) INT128 / INT256 by its bit width;
+        0 = no page path."""
+        if self.physical_type:
+            return self.physical_type
+        return {128: N.INT128, 256: N.INT256}.get(self.decimal_bits, 0)
 
     def nest_kind(self, d: int) -> str:
         if (self.struct_mask >> d) & 1:
@@ -57,7 +69,7 @@ def _leaf(c: N.LeafInfoC) -> Leaf:
     return Leaf(c.name.decode(errors="replace"), ARROW_TYPE.get(c.arrow_type, str(c.arrow_type)), c.physical_type,
                 bool(c.nullable), c.depth, [bool(c.list_nullable[i]) for i in range(d)],
                 [bool(c.large_list[i]) for i in range(d)], c.flags, c.top_field, c.struct_mask, c.map_mask,
-                [int(c.nest_id[i]) for i in range(d)])
+                [int(c.nest_id[i]) for i in range(d)], c.decimal_bits, c.decimal_precision, c.decimal_scale)
 
 
 def parse_schema(schema_bytes: bytes) -> List[Leaf]:
@@ -127,9 +139,13 @@ class StrawboatFile:
         self._check(N.lib().sb_file_upload(ctx._h, self._h, off, n, ctypes.c_void_p(out.data_ptr())))
         return out
 
-    def decoder(self, col: int, ctx: Optional[Context] = None, chunk=None):
+    def decoder(self, col: int, ctx: Optional[Context] = None, chunk=None, decimal_pages: bool = False):
         """The decoder of leaf `col` (read/deserialize.rs dispatch: primitive,
-        Boolean, Binary / Utf8, List<...>) over its uploaded chunk."""
+        Boolean, Binary / Utf8, List<...>) over its uploaded chunk.  A Decimal
+        leaf's logical type names no physical type (physical_type 0), so it
+        is refused like any leaf without one unless decimal_pages is set:
+        then a flat Decimal leaf decodes as the Int128 / Int256 pages its bit
+        width says (Leaf.page_type); read_field asks for that."""
         from .binary import BINARY, LARGE_BINARY, LARGE_UTF8, UTF8, BinaryColumnDecoder
         from .nested import ListColumnDecoder, NestedColumnDecoder
 
@@ -145,7 +161,8 @@ class StrawboatFile:
         if chunk is None:
             chunk = self.upload(col, ctx)
         metas = self.columns[col].pages
-        pt = leaf.physical_type
+        # a flat Decimal leaf reads as Int128 / Int256 pages; one under a nest is not decoded here
+        pt = leaf.page_type if leaf.depth == 0 and decimal_pages else leaf.physical_type
         if leaf.flags & ~(LEAF_STRUCT | LEAF_MAP) or not pt:
             raise N.StrawboatError(N.E_NYI, f"leaf {leaf.name}: {leaf.arrow_type} (flags {leaf.flags}) has no page path here")
         binary = pt in (BINARY, LARGE_BINARY, UTF8, LARGE_UTF8)
@@ -177,8 +194,9 @@ class StrawboatFile:
             first = self.leaves[cs[0]]
             if d == first.depth:
                 assert len(cs) == 1
-                return Field.leaf(first.physical_type, first.nullable, first.name) if first.physical_type not in _DTYPE \
-                    else Field.leaf(_DTYPE[first.physical_type], first.nullable, first.name)
+                pt = first.page_type if d == 0 else first.physical_type
+                return Field.leaf(pt, first.nullable, first.name) if pt not in _DTYPE \
+                    else Field.leaf(_DTYPE[pt], first.nullable, first.name)
             kind = first.nest_kind(d)
             groups = []  # children: consecutive leaves sharing the nest id at d + 1 (or a leaf at d + 1)
             for c in cs:
@@ -205,7 +223,7 @@ class StrawboatFile:
         fld, cols = self.field(top)
         ctx = resolve_context(ctx, None)
         if fld.kind == "leaf":
-            dec = self.decoder(cols[0], ctx)
+            dec = self.decoder(cols[0], ctx, decimal_pages=True)
             try:
                 return dec.decode()
             finally:

@@ -25,7 +25,24 @@ _PHYS = {
     np.dtype(np.int64): N.INT64, np.dtype(np.uint8): N.UINT8, np.dtype(np.uint16): N.UINT16,
     np.dtype(np.uint32): N.UINT32, np.dtype(np.uint64): N.UINT64, np.dtype(np.float32): N.FLOAT32,
     np.dtype(np.float64): N.FLOAT64, np.dtype(np.bool_): N.BOOLEAN,
+    # i128 / i256 (Decimal / Decimal256 buffers): 16- / 32-byte little-endian values
+    np.dtype("V16"): N.INT128, np.dtype("V32"): N.INT256,
 }
+
+
+def is_wide(dtype) -> bool:
+    """dtype is the 16- / 32-byte value type of an Int128 / Int256 column."""
+    try:
+        return np.dtype(dtype) in (np.dtype("V16"), np.dtype("V32"))
+    except TypeError:
+        return False
+
+
+def refuse_wide(dtype, what: str):
+    """Int128 / Int256 columns are read by ColumnDecoder and written by the
+    host encoder alone: every other path refuses them by name."""
+    if is_wide(dtype):
+        raise N.StrawboatError(N.E_NYI, f"{what}: {np.dtype(dtype).itemsize * 8}-bit integer columns are not supported")
 
 
 def physical_type(dtype) -> int:
@@ -259,8 +276,12 @@ class ColumnDecoder:
             nwords = (self.num_rows + 31) // 32
             values = torch.zeros(max(nwords, 1) * 4, dtype=torch.uint8, device=dev)
         else:
-            tdt = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[self.dtype.itemsize]
-            values = torch.empty(max(self.num_rows, 1), dtype=tdt, device=dev)
+            w = self.dtype.itemsize
+            if w >= 16:  # Int128 / Int256: (rows, W) bytes (torch allocations are 16-byte aligned)
+                values = torch.empty((max(self.num_rows, 1), w), dtype=torch.uint8, device=dev)[: self.num_rows]
+            else:
+                tdt = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[w]
+                values = torch.empty(max(self.num_rows, 1), dtype=tdt, device=dev)
         validity = None
         if self.nullable:
             nwords = (self.num_rows + 31) // 32

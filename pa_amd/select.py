@@ -42,7 +42,7 @@ import numpy as np
 
 from . import _native as N
 from .binary import BINARY, LARGE_BINARY, LARGE_UTF8, UTF8, BinaryOutC, _ow
-from .read import PageMeta, _as_device_bytes, physical_type, resolve_context
+from .read import PageMeta, _as_device_bytes, physical_type, refuse_wide, resolve_context
 
 _BINARY_TYPES = (BINARY, LARGE_BINARY, UTF8, LARGE_UTF8)
 
@@ -249,6 +249,7 @@ class SelectedColumnDecoder(_SelectedBase):
 
     def __init__(self, chunk, page_metas, dtype, nullable: bool, selection, ctx=None, packed: bool = False):
         self.dtype = np.dtype(dtype)
+        refuse_wide(self.dtype, "selective read")
         self._plan(chunk, page_metas, physical_type(self.dtype), nullable, selection, ctx, packed)
 
     def alloc_outputs(self):

@@ -18,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as N
-from .read import Context, PageMeta, _as_device_bytes, physical_type, resolve_context
+from .read import Context, PageMeta, _as_device_bytes, physical_type, refuse_wide, resolve_context
 
 
 class ColumnGroupDecoder:
@@ -30,6 +30,7 @@ class ColumnGroupDecoder:
                  ctx: Optional[Context] = None):
         import torch
 
+        refuse_wide(dtype, "ColumnGroupDecoder")
         cols = list(columns)
         if not cols:
             raise N.StrawboatError(N.E_ARG, "no columns")

@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as N
-from .read import ColumnMeta, PageMeta, physical_type
+from .read import ColumnMeta, PageMeta, physical_type, refuse_wide
 
 # CommonCompression / Compression codec ids (compression/mod.rs:64-82)
 NONE, LZ4, ZSTD, SNAPPY = 0, 1, 2, 3
@@ -92,6 +92,14 @@ def run_device_encode(name: str, ctx, device, cap: int, npages: int, call):
     return out[: olen.value], [PageMeta(metas[i].length, metas[i].num_values) for i in range(npg.value)]
 
 
+def _wide_values(values: np.ndarray) -> np.ndarray:
+    """A uint8 array of shape (n, 16) / (n, 32) is a column of Int128 / Int256
+    values (little-endian, Arrow's decimal buffers): viewed as V16 / V32."""
+    if values.dtype == np.uint8 and values.ndim == 2 and values.shape[1] in (16, 32):
+        return values.view(f"V{values.shape[1]}").reshape(-1)
+    return values
+
+
 def _take(ptr, n) -> bytes:
     b = ctypes.string_at(ptr, n) if n else b""
     N.lib().sb_free(ptr)
@@ -102,7 +110,7 @@ def encode_column(values: np.ndarray, validity=None, nullable: bool = False,
                   options: Optional[WriteOptions] = None, n_threads: int = 0) -> Tuple[bytes, List[PageMeta]]:
     """encode_chunk for one flat leaf -> (column chunk bytes, page metas)."""
     options = options or WriteOptions()
-    values = np.ascontiguousarray(values)
+    values = _wide_values(np.ascontiguousarray(values))
     n = len(values)
     phys = physical_type(values.dtype)
     if phys == N.BOOLEAN:  # compress_boolean takes the column's bitmap; pages slice it
@@ -143,6 +151,7 @@ def encode_column_device(values, validity=None, nullable: bool = False, options:
     from .read import resolve_context
 
     options = options or WriteOptions()
+    refuse_wide(getattr(values, "dtype", None) if isinstance(values, np.ndarray) else None, "encode_column_device")
     ctx = resolve_context(ctx, values)
     values = values.contiguous()
     n = values.numel()
@@ -266,7 +275,7 @@ def encode_table_device(columns: Sequence[DeviceColumn], n_streams: int = 4, dev
 def encode_page(values: np.ndarray, validity=None, nullable: bool = False,
                 options: Optional[WriteOptions] = None, seed: Optional[int] = None) -> bytes:
     options = options or WriteOptions()
-    values = np.ascontiguousarray(values)
+    values = _wide_values(np.ascontiguousarray(values))
     vb = None if validity is None else np.packbits(np.asarray(validity, bool), bitorder="little")
     out = ctypes.POINTER(ctypes.c_uint8)()
     olen = ctypes.c_uint64()

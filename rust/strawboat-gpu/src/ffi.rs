@@ -16,6 +16,7 @@ pub struct sb_leaf_info {
     pub name: [c_char; 64], pub arrow_type: i32, pub physical_type: i32, pub nullable: i32, pub depth: i32,
     pub list_nullable: [i32; SB_MAX_NEST], pub large_list: [i32; SB_MAX_NEST], pub flags: u32, pub top_field: i32,
     pub struct_mask: u32, pub map_mask: u32, pub nest_id: [i32; SB_MAX_NEST],
+    pub decimal_bits: i32, pub decimal_precision: i32, pub decimal_scale: i32,
 }
 
 #[repr(C)] #[derive(Debug, Clone, Copy, PartialEq, Eq)]

@@ -556,6 +556,12 @@ pub struct Leaf {
     pub struct_mask: u32,
     pub map_mask: u32,
     pub nest_id: Vec<i32>,
+    /// Decimal leaves: Schema.fbs `Decimal.bitWidth` (128 or 256; 0 for every
+    /// other leaf), precision and scale.  Their pages are Int128 / Int256
+    /// (physical types 16 / 17 of the C ABI), which this crate does not read yet.
+    pub decimal_bits: i32,
+    pub decimal_precision: i32,
+    pub decimal_scale: i32,
 }
 
 /// `infer_schema` + arrow2 `deserialize_schema`, flattened to leaves.
@@ -581,6 +587,9 @@ pub fn parse_schema(bytes: &[u8]) -> Result<Vec<Leaf>> {
             struct_mask: l.struct_mask,
             map_mask: l.map_mask,
             nest_id: l.nest_id[..depth].to_vec(),
+            decimal_bits: l.decimal_bits,
+            decimal_precision: l.decimal_precision,
+            decimal_scale: l.decimal_scale,
         }
     }).collect())
 }
